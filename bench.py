@@ -18,7 +18,18 @@ peers over xGMI inside the persistent launch. Total work is fixe
 before anything touches the GPU; launch_plan / spawn_ranks); under an external launcher
 (WORLD_SIZE set) --gpus must agree with it.
 
-Extra objects on the line:
+A plain run sets up, warms up, times --steps steps and prints the line (`ms_per_step` = the
+milliseconds one timed step took); everything below that needs work of its own is done only with
+--full and is null otherwise.
+
+--dump-outputs DIR: after the timed steps, what the last timed step computed is written as
+DIR/<name>.npy in the storage precision — `A` (the factorised matrix, R above V; (n, m) storage)
+and `tau` as plan.execute leaves them (N > 1: `A_rank<r>` / `tau_rank<r>`, each rank's packed tile
+columns). An array larger than its share of DUMP_BUDGET is written as a fixed sample (dump_sample:
+seeded flat indices, the same from run to run, like the seeded input).
+
+Extra objects on the line (--full):
+  check         — column norms of R against those of the input (check_output).
   roofline      — the dominant kernel (trailing-update: TSMQR/UNMQR strips on
                   v_mfma_f64_4x4x4_4b_f64): algorithmic flops of its launches / their summed
                   device time (HIP events on its own stream, a separate profiled pass),
@@ -160,6 +171,41 @@ def load_pmc(m, n, b, storage):
         return None
 
 
+DUMP_BUDGET = 64 << 20  # bytes --dump-outputs may write in all
+DUMP_SEED = 20
+
+
+def dump_sample(numel, count):
+    """The flat indices --dump-outputs keeps of an array too large to write whole: `count` seeded
+    draws from range(numel), sorted (a function of numel and count only)."""
+    import numpy as np
+    return np.sort(np.random.default_rng(DUMP_SEED).integers(0, numel, size=count, dtype=np.int64))
+
+
+def dump_outputs(path, arrays, share=1):
+    """Write each tensor of `arrays` (name -> tensor) as path/<name>.npy in its own precision (fp32
+    or fp64): whole when it fits an equal part of DUMP_BUDGET / share, else its dump_sample.
+    Returns name -> {"shape", "written", "sampled"} for the result line."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BUDGET // max(1, share) // max(1, len(arrays))
+    info = {}
+    for name, t in arrays.items():
+        flat = t.detach().contiguous().reshape(-1)
+        keep = cap // flat.element_size()
+        sampled = flat.numel() > keep
+        if sampled:
+            flat = flat[torch.from_numpy(dump_sample(flat.numel(), keep)).to(flat.device)]
+        out = flat.cpu().numpy()
+        if not sampled:
+            out = out.reshape(tuple(t.shape))
+        assert out.dtype in (np.float32, np.float64)
+        np.save(os.path.join(path, name + ".npy"), out)
+        info[name] = {"shape": list(t.shape), "written": int(out.size), "sampled": sampled}
+    return info
+
+
 def check_output(A0, A, m, n):
     """Cheap correctness check of the final factorisation (outside the timed region): Q is
     orthogonal, so every column of R has the norm of the same column of A."""
@@ -197,6 +243,43 @@ def check_owned_columns(A0, A, m, n, b, rank, world, owned=None, packed=False):
     if not rel <= tol:
         raise RuntimeError(f"bench: rank {rank}: factorisation check failed (column-norm error {rel:.3e} > {tol})")
     return rel
+
+
+def roofline_pass(torch, plan, A0, A, tau, stream, m, n, b, world, storage, value):
+    """--full: one more factorisation with the engine's per-launch profiling on, and the `roofline`
+    object of the result line from it (value: the headline GFLOP/s)."""
+    # profiled pass (outside the timed region): per-launch device time of the dominant kernel
+    plan.set_profile(True)
+    A.copy_(A0)
+    plan.execute(A, tau, stream=stream)
+    torch.cuda.synchronize()
+    st = plan.stats()
+    plan.set_profile(False)
+    uf = update_flops(m, n, b)
+    # per GPU: its share of the update flops (1/N of the job at N > 1) over its launch time
+    achieved = uf / world / (st["ms_update"] * 1e-3) / 1e12 if st["ms_update"] > 0 else None
+    peak = FP64_MFMA_PEAK_TFLOPS if storage == "f64" else FP32_MFMA_PEAK_TFLOPS
+    pmc = load_pmc(m, n, b, storage) if world == 1 else None
+    traffic = pmc.get("update_hbm_bytes_per_launch") if pmc else None
+    roof = {
+        "bound": "mfma",
+        "kernel": "k_flow (persistent engine; TSMQR/UNMQR strips on " +
+                  ("v_mfma_f64_4x4x4_4b_f64)" if storage == "f64" else "v_mfma_f32_16x16x4_f32)"),
+        "achieved": round(achieved, 3) if achieved else None,
+        "peak": peak,
+        "unit": "TFLOP/s",
+        "frac": round(achieved / peak, 4) if achieved else None,
+        "traffic": traffic,
+        "executed_flops": pmc.get("executed_mfma_flops") if pmc else None,
+        "mfma_util": round(pmc["mfma_util"], 4) if pmc and pmc.get("mfma_util") is not None else None,
+        "pmc_source": "profiles/pmc_summary.json (rocprofv3 --pmc, tools/pmc_traffic.sh)" if pmc else None,
+        "launches": st["n_update"],
+        "avg_launch_ms": round(st["ms_update"] / max(1, st["n_update"]), 4),
+        "algorithmic_flops_per_launch": round(uf / max(1, st["n_update"])),
+        "panel_kernel_ms_total": round(st["ms_panel"], 3),
+        "whole_factorisation_frac_of_peak": round(value / 1e3 / (world * peak), 4),
+    }
+    return roof
 
 
 def stage_budget(torch, share=1):
@@ -332,6 +415,12 @@ def main():
     ap.add_argument("--storage", choices=["f64", "f32"], default="f64",
                     help="matrix element type: f64 (fp64 MFMA chains) or f32 (fp32 MFMA chains, fp64 panel "
                          "factorisation; BASELINE configs[4])")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the output check, the profiled "
+                         "roofline pass, the host-pointer timing, the CPU baseline and (N > 1) the single-GPU leg; "
+                         "the --no-* options below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (A, tau) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-api", action="store_true",
                     help="skip the PCIe-inclusive host-pointer timing (tqr_*geqrt_host)")
@@ -341,6 +430,8 @@ def main():
     ap.add_argument("--no-single-leg", action="store_true",
                     help="N > 1: skip rank 0's single-GPU timing of the same matrix (strong_scaling)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import tqr
@@ -372,11 +463,11 @@ def main():
         os.environ["TQR_FLOW_GRID"] = str(max(1, ncu // world))
     full_grid = int(os.environ.get("TQR_FLOW_GRID", ncu)) >= ncu  # (engine.hip: the segment-length rule)
 
-    # strong scaling, self-contained: before the N-rank region, rank 0 factorises the same m x n
+    # strong scaling, self-contained (--full): before the N-rank region, rank 0 factorises the same m x n
     # matrix on its GPU alone (single-GPU engine, same steps / warmup / input handling); the others wait
     single = None
     if dist:
-        if rank == 0 and not args.no_single_leg:
+        if rank == 0 and args.full and not args.no_single_leg:
             single = single_gpu_leg(tqr, torch, m, n, b, dt, args.steps, args.warmup)
         dist.barrier()
 
@@ -446,10 +537,15 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         el = float(tt.item())
     engine_status("timed steps")
-    Afin = As[-1] if staged and args.steps else A  # the last timed step's output
-    if world == 1:
+    Afin = As[-1] if staged else A  # the last timed step's output
+    dumped = None
+    if args.dump_outputs:
+        sfx = f"_rank{rank}" if dist else ""
+        dumped = dump_outputs(args.dump_outputs, {"A" + sfx: Afin, "tau" + sfx: tau}, share=world)
+    ok_rel = None  # (the output check: --full)
+    if args.full and world == 1:
         ok_rel = check_output(A0, Afin, m, n)
-    else:
+    elif args.full:
         try:
             ok_rel = check_owned_columns(A0, Afin, m, n, b, rank, world, plan.owned_cols(), packed=True)
         except RuntimeError as e:
@@ -505,39 +601,11 @@ def main():
     total_flops = qr_flops(m, n) * args.steps
     value = total_flops / el / 1e9
 
-    # profiled pass (outside the timed region): per-launch device time of the dominant kernel
-    plan.set_profile(True)
-    A.copy_(A0)
-    plan.execute(A, tau, stream=stream)
-    torch.cuda.synchronize()
-    st = plan.stats()
-    plan.set_profile(False)
-    uf = update_flops(m, n, b)
-    # per GPU: its share of the update flops (1/N of the job at N > 1) over its launch time
-    achieved = uf / world / (st["ms_update"] * 1e-3) / 1e12 if st["ms_update"] > 0 else None
-    peak = FP64_MFMA_PEAK_TFLOPS if args.storage == "f64" else FP32_MFMA_PEAK_TFLOPS
-    pmc = load_pmc(m, n, b, args.storage) if world == 1 else None
-    traffic = pmc.get("update_hbm_bytes_per_launch") if pmc else None
-    roof = {
-        "bound": "mfma",
-        "kernel": "k_flow (persistent engine; TSMQR/UNMQR strips on " +
-                  ("v_mfma_f64_4x4x4_4b_f64)" if args.storage == "f64" else "v_mfma_f32_16x16x4_f32)"),
-        "achieved": round(achieved, 3) if achieved else None,
-        "peak": peak,
-        "unit": "TFLOP/s",
-        "frac": round(achieved / peak, 4) if achieved else None,
-        "traffic": traffic,
-        "executed_flops": pmc.get("executed_mfma_flops") if pmc else None,
-        "mfma_util": round(pmc["mfma_util"], 4) if pmc and pmc.get("mfma_util") is not None else None,
-        "pmc_source": "profiles/pmc_summary.json (rocprofv3 --pmc, tools/pmc_traffic.sh)" if pmc else None,
-        "launches": st["n_update"],
-        "avg_launch_ms": round(st["ms_update"] / max(1, st["n_update"]), 4),
-        "algorithmic_flops_per_launch": round(uf / max(1, st["n_update"])),
-        "panel_kernel_ms_total": round(st["ms_panel"], 3),
-        "whole_factorisation_frac_of_peak": round(value / 1e3 / (world * peak), 4),
-    }
+    roof = None
+    if args.full:
+        roof = roofline_pass(torch, plan, A0, A, tau, stream, m, n, b, world, args.storage, value)
     host_api = None
-    if world == 1 and not args.no_host_api:
+    if args.full and world == 1 and not args.no_host_api:
         # the reference's calling convention (host matrix in, factorised host matrix out): pageable
         # host array -> pinned staging -> HBM, factorisation, and back (outside the timed region;
         # reported beside, never as, the value)
@@ -569,7 +637,7 @@ def main():
                             "caller's array page-locked for the call and read / written by the launch directly"}
         del Ah, Th
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # (minutes of host work with no other output: a heartbeat on stderr every 30 s, the ctypes
         # calls release the GIL; stdout carries the one result line only)
         done = threading.Event()
@@ -621,6 +689,8 @@ def main():
             "dist": dist_info,
             "strong_scaling": strong,
             "host_api": host_api,
+            "outputs": dumped,
+            "full": args.full,
         }
         print(json.dumps(line))
     if dist:

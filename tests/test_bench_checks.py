@@ -127,6 +127,31 @@ def test_check_owned_columns_packed_storage(world):
             bench.check_owned_columns(A0[rows], Ab, m, n, b, rank, world, own, packed=True)
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: an array within its share of the budget is written whole in its own
+    precision, a larger one as the same seeded sample every time, and the total stays in budget."""
+    import numpy as np
+    g = torch.Generator().manual_seed(1)
+    A = torch.randn(96, 160, dtype=torch.float64, generator=g)
+    tau = torch.randn(3, 160, dtype=torch.float32, generator=g)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 16384)  # 8192 bytes each: 1024 fp64 of A, tau whole
+    info = bench.dump_outputs(str(tmp_path / "a"), {"A": A, "tau": tau})
+    bench.dump_outputs(str(tmp_path / "b"), {"A": A.clone(), "tau": tau.clone()})
+    a, t = np.load(tmp_path / "a" / "A.npy"), np.load(tmp_path / "a" / "tau.npy")
+    assert a.dtype == np.float64 and t.dtype == np.float32
+    assert t.shape == (3, 160) and np.array_equal(t, tau.numpy())
+    idx = bench.dump_sample(A.numel(), 1024)
+    assert a.shape == (1024,) and np.array_equal(a, A.numpy().reshape(-1)[idx])
+    assert idx.min() >= 0 and idx.max() < A.numel() and np.all(np.diff(idx) >= 0)
+    assert np.array_equal(a, np.load(tmp_path / "b" / "A.npy"))
+    assert a.nbytes + t.nbytes <= 16384
+    assert info["A"] == {"shape": [96, 160], "written": 1024, "sampled": True}
+    assert info["tau"] == {"shape": [3, 160], "written": 480, "sampled": False}
+    # N ranks share the budget
+    bench.dump_outputs(str(tmp_path / "c"), {"A_rank1": A, "tau_rank1": tau}, share=2)
+    assert np.load(tmp_path / "c" / "A_rank1.npy").shape == (512,)
+
+
 def test_chain_segment_length_rule(monkeypatch):
     """bench.seglen_of mirrors engine.hip env_seglen: 8 on one or two ranks, 2 from four ranks on
     (tools/sched_sim.py seglen), TQR_SEGLEN overrides."""

@@ -10,7 +10,7 @@ for r in $(seq 1 $R); do
   for V in "$@"; do
     L=${V%%:*}; E=""; [ "$V" != "$L" ] && E=${V#*:}
     tag=$(echo "${L%.so}_${E}" | tr ',=' '__')
-    env TQR_LIB=$L $(echo $E | tr ',' ' ') timeout -k 10 240 python bench.py --no-cpu-baseline --no-host-api ${BENCH_ARGS:-} > $O/${tag}_$r.json 2>> $O/ab.err || { echo "bench $V failed"; tail -5 $O/ab.err; exit 1; }
+    env TQR_LIB=$L $(echo $E | tr ',' ' ') timeout -k 10 240 python bench.py --full --no-cpu-baseline --no-host-api ${BENCH_ARGS:-} > $O/${tag}_$r.json 2>> $O/ab.err || { echo "bench $V failed"; tail -5 $O/ab.err; exit 1; }
     python -c "import json;d=json.load(open('$O/${tag}_$r.json'));print('$V', d['ms_per_step'], d['roofline']['avg_launch_ms'], d['roofline']['frac'])"
   done
 done

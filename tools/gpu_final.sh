@@ -13,13 +13,13 @@ if [ "${TESTS:-1}" = 1 ]; then
   tail -2 $OUT/pytest_gpu.log
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 700 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { echo "bench failed"; tail -20 $OUT/bench_default.err; exit 1; }
+  timeout -k 10 700 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { echo "bench failed"; tail -20 $OUT/bench_default.err; exit 1; }
   cat $OUT/bench_default.json
-  timeout -k 10 400 python bench.py --storage f32 --rows 32768 --cols 32768 > $OUT/bench_f32_c5.json 2> $OUT/bench_f32_c5.err || { echo "bench f32 failed"; tail -20 $OUT/bench_f32_c5.err; exit 1; }
+  timeout -k 10 400 python bench.py --full --storage f32 --rows 32768 --cols 32768 > $OUT/bench_f32_c5.json 2> $OUT/bench_f32_c5.err || { echo "bench f32 failed"; tail -20 $OUT/bench_f32_c5.err; exit 1; }
   cat $OUT/bench_f32_c5.json
 fi
 if [ "${C4:-0}" = 1 ]; then  # the 65536 x 16384 one-GPU line (the multi-GPU model's calibration)
-  timeout -k 10 300 python bench.py --rows 65536 --cols 16384 --no-cpu-baseline --no-host-api > $OUT/bench_c4.json 2> $OUT/bench_c4.err || { echo "bench c4 failed"; tail -20 $OUT/bench_c4.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --rows 65536 --cols 16384 --no-cpu-baseline --no-host-api > $OUT/bench_c4.json 2> $OUT/bench_c4.err || { echo "bench c4 failed"; tail -20 $OUT/bench_c4.err; exit 1; }
   cat $OUT/bench_c4.json
 fi
 if [ "${TIMELINE:-0}" = 1 ]; then  # the last steps' task timeline (stamps build libtqr_fst.so)

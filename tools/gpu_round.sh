@@ -11,7 +11,7 @@ if [ "${TESTS:-1}" = 1 ]; then
   timeout -k 10 600 python -u -m pytest tests -q -x -m gpu --timeout 120 --timeout-method thread ${PYTEST_ARGS:-} > $OUT/pytest_gpu.log 2>&1 || { echo "pytest failed"; tail -40 $OUT/pytest_gpu.log; exit 1; }
   tail -2 $OUT/pytest_gpu.log
 fi
-timeout -k 10 300 python bench.py ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err || { echo "bench failed"; tail -20 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
 if [ "${FST:-1}" = 1 ] && [ -f gpu-tiled-qr-decomposition_amd/libtqr_fst.so ]; then
   timeout -k 10 120 python tools/flowstamps.py 16384 > $OUT/flowstamps.txt 2>&1 || { echo "flowstamps failed"; tail -20 $OUT/flowstamps.txt; exit 1; }
