@@ -88,6 +88,16 @@ def lib():
     L.tqr_dist_owner.argtypes = [_P, _I]
     L.tqr_dgeqrt_host.argtypes = [_P, _P, _I, _I, _I, _I]
     L.tqr_sgeqrt_host.argtypes = [_P, _P, _I, _I, _I, _I]
+    L.tqr_apply_create.argtypes = [ctypes.POINTER(_P), _I, _I, _I, _I]
+    L.tqr_apply_create.restype = _I
+    L.tqr_apply_workspace_bytes.argtypes = [_P]
+    L.tqr_apply_workspace_bytes.restype = ctypes.c_size_t
+    L.tqr_apply_prepare.argtypes = [_P, _P, _I, _P, _P]
+    L.tqr_apply_prepare.restype = _I
+    L.tqr_apply_q.argtypes = [_P, _I, _P, _I, _P, _I, _I, _P]
+    L.tqr_apply_q.restype = _I
+    L.tqr_apply_destroy.argtypes = [_P]
+    L.tqr_apply_destroy.restype = None
     _lib = L
     return L
 
@@ -367,6 +377,103 @@ def expand_tau(tau_compact, m, n, b):
     for k in range(min(m, n) // b):
         T[k * b, k * b:] = tau_compact[k, k * b:]
     return T
+
+
+def compact_tau(T, m, n, b):
+    """The reference's m x n tau matrix ((n, m) array) -> compact (kmax, m): the inverse of
+    expand_tau (column k*b, rows k*b.., becomes row k)."""
+    kmax = min(m, n) // b
+    tc = np.zeros((kmax, m), dtype=T.dtype)
+    for k in range(kmax):
+        tc[k, k * b:] = T[k * b, k * b:m]
+    return tc
+
+
+# ---- apply Q / Q^T of a finished factorisation; least squares -------------------------------
+def _stream_handle(stream):
+    """hipStream_t of a torch stream, a raw handle (int), or None (the default stream)."""
+    return _P(getattr(stream, "cuda_stream", stream) or 0)
+
+
+class ApplyQ:
+    """C <- Q^T C / C <- Q C with the factors a TiledQR left on the device (tqr_apply, include/tqr.h
+    "apply"). Create once per shape, prepare() once per factorisation (rebuilds the T factors into
+    the handle's workspace), then apply() to any number of right-hand sides. Single GPU."""
+
+    def __init__(self, m, n, b, dtype):
+        self.m, self.n, self.b = m, n, b
+        self.dtype = dtype if isinstance(dtype, int) else _dtype_code(dtype)
+        self.kmax = min(m, n) // b if b > 0 else 0
+        self.h = None
+        h = _P()
+        check(lib().tqr_apply_create(ctypes.byref(h), m, n, b, self.dtype), "tqr_apply_create")
+        self.h = h
+
+    def workspace_bytes(self):
+        return int(lib().tqr_apply_workspace_bytes(self.h))
+
+    def prepare(self, A, tau, ldda=None, stream=None):
+        """A (n, ldda): the factorised matrix; tau (kmax, m) compact. Stream-ordered."""
+        ldda = ldda or A.shape[-1]
+        check(lib().tqr_apply_prepare(self.h, _ptr(A), ldda, _ptr(tau), _stream_handle(stream)), "tqr_apply_prepare")
+
+    def apply(self, A, C, trans=True, nrhs=None, ldda=None, lddc=None, stream=None):
+        """C (nrhs, lddc) <- Q^T C (trans) or Q C, in place; A as given to prepare(). nrhs, ldda and
+        lddc default to the tensors' shapes. Stream-ordered."""
+        ldda = ldda or A.shape[-1]
+        lddc = lddc or C.shape[-1]
+        nrhs = C.shape[0] if nrhs is None else nrhs
+        check(lib().tqr_apply_q(self.h, 1 if trans else 0, _ptr(A), ldda, _ptr(C), nrhs, lddc, _stream_handle(stream)),
+              "tqr_apply_q")
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().tqr_apply_destroy(self.h)
+        except Exception:
+            pass
+
+
+def lstsq(F, tau, B, b):
+    """Least squares min |A x - b| for every column of B from a finished factorisation of the
+    m x n matrix A, m >= n: F (n, m) and tau (kmax, m) as TiledQR.execute left them, B (nrhs, m), all
+    device tensors of one dtype. B is overwritten with Q^T B (the apply kernel); R X = (Q^T B)[:n] is
+    then one triangular solve on the upper triangle of F (torch: n^2 nrhs flops of plumbing next to
+    the apply's ~4 m n nrhs). Returns X as (nrhs, n) and the residual norms |A x - b| per column,
+    taken from rows n .. m-1 of Q^T B."""
+    import torch
+    n, m = F.shape
+    if m < n:
+        raise TQRError(f"lstsq needs m >= n, got {m} x {n}")
+    if B.shape[-1] != m or B.dtype != F.dtype or tau.dtype != F.dtype:
+        raise TQRError("lstsq: B must be (nrhs, m) and F, tau, B of one dtype")
+    ap = ApplyQ(m, n, b, F.dtype)
+    cs = torch.cuda.current_stream()  # the torch ops below are ordered behind the apply on it
+    ap.prepare(F, tau, stream=cs)
+    ap.apply(F, B, trans=True, stream=cs)
+    # column-major R is the transpose of the torch view: X^T R^T = Y^T with R^T lower triangular
+    Rt = torch.tril(F[:, :n])
+    X = torch.linalg.solve_triangular(Rt, B[:, :n], upper=False, left=False)
+    res = torch.linalg.vector_norm(B[:, n:], dim=1)
+    return X, res
+
+
+def apply_q_host(F, T, C, b, trans=True):
+    """Convenience for host arrays: F, T (n, m) as geqrt_host produces them (T: the reference's
+    m x n tau matrix), C (nrhs, m). Staged through torch to the GPU; returns the new C."""
+    import torch
+    n, m = F.shape
+    if T.shape != F.shape or C.ndim != 2 or C.shape[1] != m or C.dtype != F.dtype or T.dtype != F.dtype:
+        raise TQRError("apply_q_host: F, T (n, m) and C (nrhs, m) of one dtype")
+    ap = ApplyQ(m, n, b, F.dtype)
+    dF = torch.tensor(np.ascontiguousarray(F), device="cuda")  # (copies: read-only inputs are fine)
+    dt = torch.tensor(compact_tau(T, m, n, b), device="cuda")
+    dC = torch.tensor(np.ascontiguousarray(C), device="cuda")
+    cs = torch.cuda.current_stream()
+    ap.prepare(dF, dt, stream=cs)
+    ap.apply(dF, dC, trans=trans, stream=cs)
+    torch.cuda.synchronize()
+    return dC.cpu().numpy()
 
 
 # ---- single tile ops (host pointers; the reference's SGEQRF/SLARFT/STSQRF/SSSRFT) --------

@@ -106,6 +106,41 @@ int tqr_plan_stats(const tqr_plan* plan, int* nlaunch_update, double* ms_update,
 /* Number of flat-tree tasks (reference calcTotalTasks, src/gpucalc.cu:1546, for all m,n). */
 long tqr_total_tasks(int m, int n, int b);
 
+/* ---- apply: C <- Q^T C or C <- Q C with the factors of a finished factorisation -------------
+ * (the ormqr to the plan's geqrf). dA, ldda and dtau_compact are what tqr_plan_execute left on the
+ * device: R, the V tiles and the compact tau; the apply only reads them. Q is the full m x m
+ * orthogonal factor (Q^T A = [R; 0]). C is m x nrhs, column-major, of the handle's dtype, with
+ * leading dimension lddc >= m; nrhs >= 1 need not be a multiple of anything. Rows >= m and columns
+ * >= nrhs of C's allocation are not touched. ldda and lddc obey the library's leading-dimension
+ * bound (above).
+ *   TQR_TRANS:   for k = 0 .. kmax-1: C_k <- UNMQR(V_kk) C_k, then for l = k+1 .. p-1:
+ *                [C_k; C_l] <- TSMQR(V_lk) [C_k; C_l] — what the factorisation did to a trailing
+ *                column (C_i = row tile i of C, p = m/b);
+ *   TQR_NOTRANS: the exact reverse (k descending, l descending then the UNMQR tile, each block
+ *                reflector untransposed), so Q (Q^T C) = C. Q itself is the apply to an identity.
+ * fp32 handles load and store float and compute in fp64, as the tile updates of the single-tile API.
+ * One workgroup per 64 columns of C walks the whole reflector sequence serially; workgroups never
+ * wait for each other (the kernel has no counters or flags), so a narrow C uses few CUs.
+ * Single-GPU factorisations only: the packed per-rank storage of a tqr_dist_plan is not supported.
+ *
+ * create validates as tqr_plan_create (before any device call) and allocates the T workspace:
+ * one 32 x 33 fp64 image (b < 32: b x (b+1)), padded to whole KiB, per 32-reflector group of every
+ * tile (l,k), l >= k, k < kmax — tqr_apply_workspace_bytes. prepare and apply_q allocate nothing.
+ * prepare rebuilds the T factors from V and tau (once per factorisation); apply_q before the first
+ * successful prepare returns TQR_EINVAL. Both are stream-ordered and return once enqueued.
+ * Ordering on one handle: an apply_q's stream first waits for the last prepare (an event), and a
+ * prepare's stream first waits for every apply_q enqueued since the previous prepare — a prepare
+ * never overlaps an apply of its handle on the GPU, whatever the streams. Applies only read the
+ * workspace: two apply_q calls of one handle on different streams may overlap. The caller keeps
+ * dA and dtau unchanged while work that reads them is in flight, as with any device buffer. */
+typedef struct tqr_apply tqr_apply;
+enum tqr_trans { TQR_NOTRANS = 0, TQR_TRANS = 1 };
+int tqr_apply_create(tqr_apply** ap, int m, int n, int b, int dtype);
+size_t tqr_apply_workspace_bytes(const tqr_apply* ap);
+int tqr_apply_prepare(tqr_apply* ap, const void* dA, int ldda, const void* dtau_compact, void* stream);
+int tqr_apply_q(tqr_apply* ap, int trans, const void* dA, int ldda, void* dC, int nrhs, int lddc, void* stream);
+void tqr_apply_destroy(tqr_apply* ap);
+
 /* ---- multi-GPU: tile-column partition, one process per GPU ---------------------------------
  * Rank r owns the tile columns j with tqr_dist_owner(j) == r — snake order over the ranks
  * (0..W-1, W-1..0, 0..W-1, ...: every rank's columns sum to the same index total, balancing the

@@ -1,0 +1,140 @@
+"""Apply benchmark: tqr_apply_prepare and tqr_apply_q (both directions) on a GPU
+factorisation, device time from events after a warm-up, best of `reps` runs.
+Cases: fp64 4096^2 b=128 and 16384^2 b=256, nrhs in {64, n} (or "m:b" arguments for other squares).
+One JSON line per case. An apply counts 4 b^2 nrhs flop per TSMQR tile and 2 b^2 nrhs per UNMQR tile.
+Two yardsticks from the same process:
+  (a) tqr_tile_batch DAPP — the same inner loop in one launch of independent blocks, launch and V
+      traffic at their best — with as many b-column blocks as the apply has TSMQR tile updates (capped
+      by the batch's 32-bit device matrix), reported per block;
+  (b) torch.geqrf + torch.ormqr (Q^T C) on the same shape, "unavailable" if torch cannot run them here.
+Usage: python tools/apply_bench.py [--reps N] [--no-torch] [m:b ...]"""
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpu-tiled-qr-decomposition_amd"))
+import tqr  # noqa: E402
+
+
+def parse(argv):
+    reps, use_torch, shapes = 3, True, []
+    it = iter(argv)
+    for a in it:
+        if a == "--reps":
+            reps = int(next(it))
+        elif a == "--no-torch":
+            use_torch = False
+        else:
+            m, b = a.split(":")
+            shapes.append((int(m), int(b)))
+    return reps, use_torch, shapes or [(4096, 128), (16384, 256)]
+
+
+def tile_counts(m, n, b):
+    """(TSMQR tiles, UNMQR tiles) one column block of C passes through."""
+    p, kmax = m // b, min(m, n) // b
+    return sum(p - k - 1 for k in range(kmax)), kmax
+
+
+def apply_flops(m, n, b, nrhs):
+    ts, ge = tile_counts(m, n, b)
+    return (4.0 * ts + 2.0 * ge) * b * b * nrhs
+
+
+def timed(fn, reps):
+    """best device time (ms) of fn() over `reps` runs after one warm-up run"""
+    import torch
+    fn()
+    torch.cuda.synchronize()
+    best = None
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ms = e0.elapsed_time(e1)
+        best = ms if best is None else min(best, ms)
+    return best
+
+
+def dapp_yardstick(b, want, reps):
+    """(us per block, blocks) of one tqr_tile_batch DAPP launch of min(want, what fits) blocks."""
+    L = tqr.lib()
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    rng = np.random.default_rng(5)
+    V = (rng.uniform(-0.5, 0.5, (b, b)) / np.sqrt(b)).astype(np.float64)
+    tau = 2.0 / (1.0 + (V * V).sum(axis=1))  # orthogonal reflectors [e_j; V column j] (V[col, row])
+    blk = rng.uniform(-1, 1, (b, 2 * b))
+    nb = max(1, min(want, (0x7fffffff // (8 * 2 * b * b)) - 1))
+    ms, best = ctypes.c_float(), None
+    for rep in range(reps + 1):
+        rc = L.tqr_tile_batch(tqr.TQR_F64, tqr.DAPP, b, nb, vp(V), b, vp(tau), vp(blk), 2 * b, None, 0, ctypes.byref(ms))
+        if rc != 0:
+            return None, nb
+        if rep > 0:  # (run 0 is the warm-up)
+            best = ms.value if best is None else min(best, ms.value)
+    return best * 1e3 / nb, nb
+
+
+def torch_yardstick(m, n, nrhs, reps):
+    import torch
+    try:
+        A = (torch.randint(0, 201, (m, n), device="cuda", dtype=torch.float64) - 100.0) / 100.0
+        C = torch.randn((m, nrhs), device="cuda", dtype=torch.float64)
+        fac = {}
+
+        def geqrf():
+            fac["a"], fac["tau"] = torch.geqrf(A)
+
+        t_f = timed(geqrf, reps)
+        t_o = timed(lambda: torch.ormqr(fac["a"], fac["tau"], C, left=True, transpose=True), reps)
+        return {"geqrf_ms": round(t_f, 3), "ormqr_qt_ms": round(t_o, 3)}
+    except Exception as e:  # no rocSOLVER path for this call on this build
+        return f"unavailable ({type(e).__name__})"
+
+
+def main(argv):
+    import torch
+    reps, use_torch, shapes = parse(argv)
+    assert torch.cuda.is_available(), "apply_bench.py measures on the GPU only"
+    cs = torch.cuda.current_stream()
+    for m, b in shapes:
+        n = m
+        A = torch.empty((n, m), dtype=torch.float64, device="cuda")
+        tau = torch.zeros((n // b, m), dtype=torch.float64, device="cuda")
+        tqr.fill_randzo(A, m, n, 5)
+        plan = tqr.TiledQR(m, n, b, torch.float64)
+        plan.execute(A, tau)
+        plan.status()
+        ap = tqr.ApplyQ(m, n, b, torch.float64)
+        t_prep = timed(lambda: ap.prepare(A, tau, stream=cs), reps)
+        ts, ge = tile_counts(m, n, b)
+        for nrhs in (64, n):
+            C = torch.empty((nrhs, m), dtype=torch.float64, device="cuda")
+            tqr.fill_randzo(C, m, nrhs, 9)
+            t_qt = timed(lambda: ap.apply(A, C, trans=True, stream=cs), reps)
+            t_q = timed(lambda: ap.apply(A, C, trans=False, stream=cs), reps)
+            fl = apply_flops(m, n, b, nrhs)
+            nupd = ts * ((nrhs + b - 1) // b)  # TSMQR tile updates in b-column blocks
+            y_us, y_nb = dapp_yardstick(b, nupd, reps)
+            rec = {"dtype": "f64", "m": m, "n": n, "b": b, "nrhs": nrhs,
+                   "workspace_bytes": ap.workspace_bytes(), "prepare_ms": round(t_prep, 3),
+                   "apply_qt_ms": round(t_qt, 3), "apply_q_ms": round(t_q, 3),
+                   "gflops_qt": round(fl / t_qt / 1e6, 1), "gflops_q": round(fl / t_q / 1e6, 1),
+                   "tsmqr_updates": nupd, "us_per_tsmqr_update_qt": round(t_qt * 1e3 / nupd, 3),
+                   "us_per_tsmqr_update_q": round(t_q * 1e3 / nupd, 3),
+                   "yardstick_dapp_us_per_block": None if y_us is None else round(y_us, 3),
+                   "yardstick_dapp_blocks": y_nb,
+                   "yardstick_torch": torch_yardstick(m, n, nrhs, max(1, reps - 1)) if use_torch else "skipped"}
+            print(json.dumps(rec), flush=True)
+            del C
+        del ap, plan, A, tau
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
