@@ -23,8 +23,6 @@
 
 namespace tqr {
 
-using ShapeR = FlowShape<4, 32, 1>;  // one 4-wave workgroup per CU, 64-column strips, 32-reflector groups
-
 template <int N>
 __device__ __forceinline__ bool res_sync_n(bool ok0, bool poller, int* sflag, int& par) {
   return ca_sync<N>(ok0, poller, sflag, par);

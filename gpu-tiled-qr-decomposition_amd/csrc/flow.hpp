@@ -31,11 +31,10 @@
 // spin is bounded (FLOW_TIMEOUT without progress of the host transfers: timed_out); on timeout an
 // error word is set and all workgroups drain.
 #pragma once
+#include "flow_list.hpp"
 #include "tiles.hpp"
 
 namespace tqr {
-
-constexpr int T_CHAIN = 4;
 
 // Diagnostic build only (make flowstamps): per-workgroup s_memrealtime sums by activity.
 // Every FST(c) charges the time since the previous stamp to category c (LDS-resident sums,
@@ -125,20 +124,7 @@ constexpr int FLOW_NW = FLOW_NT / 64;      // waves
 constexpr int FLOW_SW = 16 * FLOW_NW;      // strip width (columns) of a chain task
 constexpr bool FLOW_PF = true;
 
-// Engine shapes. ShapeW8 is the form above (one 8-wave workgroup per CU, 128-column chain strips,
-// 32-reflector groups): the default. ShapeW4 (round 4, fp64 under TQR_FLOW_SHAPE=w4): TWO
-// independent 4-wave workgroups per CU, 64-column chain strips, 16-reflector groups — half the LDS
-// images (76 KiB per workgroup, so two fit in the CU's 160 KiB), the two workgroups running
-// different tasks, so that one's strip hand-over, barrier skew and dependent-MFMA tails could run
-// beside the other's MFMA stream. Measured: no gain — the chain loop alone is 3-4 % slower
-// (tools/ubench/chain2_bench.hip: the hand-over's cost is not hidden by the co-resident workgroup,
-// with or without the two out of phase) and the factorisation 9 % (138.6 vs 126.7 ms at 16384^2).
-template <int NW_, int IB_, int WPC_>
-struct FlowShape {
-  static constexpr int NW = NW_, NT = 64 * NW_, SW = 16 * NW_, IB = IB_, WPC = WPC_;
-};
-using ShapeW8 = FlowShape<8, 32, 1>;
-using ShapeW4 = FlowShape<4, 16, 2>;
+// (the engine shapes FlowShape / ShapeW8 / ShapeW4 / ShapeR: flow_list.hpp)
 // the tile geometry a shape runs at (groups of min(B, IB) reflectors)
 template <int B, class C>
 using FGeo = Geo<B, (B < C::IB ? B : C::IB)>;
@@ -256,42 +242,8 @@ struct FlowArgs {
   int chain_asm;
 };
 
-// Multi-GPU owner of tile column j (its panel and all its updates): "snake" order over the ranks
-// (0..W-1, W-1..0, 0..W-1, ...), so that every rank's columns sum to the same index total — the
-// chain work of a column grows with its index, and the plain cyclic j % W left the last rank 11 %
-// more work at 65536x16384 on 8 ranks (tools/sched_sim.py dist: S(8) 5.39 vs 5.20).
-// cyclic = 1 (TQR_DIST_PART=cyclic, A/B diagnostics only) restores j % W.
-__host__ __device__ inline int tile_owner(int j, int world, int cyclic = 0) {
-  const int blk = j / world, r = j - blk * world;
-  if (cyclic) return r;
-  return (blk & 1) ? world - 1 - r : r;
-}
-
-// Segment length of chain (k, j): the last `tail` steps' chains tail_sl elements per segment (their
-// elements then pipeline group by group over workgroups instead of running one after the other in
-// one: the factorisation's tail is a few short columns per step on the critical path); else the
-// lookahead column (j = k+1) may use its own (seglen_la), and the last la_tail steps' lookahead
-// column one element per segment (engine.hip FlowKnobs).
-__host__ __device__ inline int seglen_of_chain(int k, int j, int kmax, int seglen, int seglen_la, int la_tail,
-                                               int tail = 0, int tail_sl = 1) {
-  if (k >= kmax - tail) return tail_sl;
-  if (j != k + 1) return seglen;
-  return k >= kmax - la_tail ? 1 : seglen_la;
-}
-// The last `ualone` steps' lookahead column (j = k+1) runs its UNMQR element alone in segment 0:
-// the element that finishes the next diagonal tile, TSMQR(k+1, k+1, k), then starts segment 1,
-// pipelined group by group behind the UNMQR (Ac) instead of running after it in the same task.
-__host__ __device__ inline bool unmqr_alone(int k, int j, int kmax, int ualone) { return j == k + 1 && k >= kmax - ualone; }
-// segments of chain (k, j) with segment length sl: rows k+1 .. p-1 in runs of sl, after the
-// UNMQR-only segment when unmqr_alone; the segment holding row i > k
-__host__ __device__ inline int nseg_of_chain(int k, int j, int p, int kmax, int sl, int ualone) {
-  const int rows = p - k - 1;
-  if (rows <= 0) return 1;
-  return (rows + sl - 1) / sl + (unmqr_alone(k, j, kmax, ualone) ? 1 : 0);
-}
-__host__ __device__ inline int seg_of_row(int k, int j, int i, int kmax, int sl, int ualone) {
-  return (i - k - 1) / sl + (unmqr_alone(k, j, kmax, ualone) ? 1 : 0);
-}
+// (tile_owner, seglen_of_chain, unmqr_alone, nseg_of_chain, seg_of_row — the arithmetic the host
+// planner shares with the kernels: flow_list.hpp)
 
 // ---- synchronisation ---------------------------------------------------------------------
 // Counter accesses go through global (address-space 1) pointers: a generic pointer makes them

@@ -22,7 +22,6 @@
 
 namespace tqr {
 
-constexpr int T_UP = 5, T_DOWN = 6;
 constexpr int XFER_AUX_HOST = 17;  // sc0 | sc1: system scope
 
 // thread FLOW_PT: is tile column j final? (see the header; the counts mirror build_flow_plan)

@@ -88,6 +88,7 @@ def lib():
     L.tqr_dist_owner.argtypes = [_P, _I]
     L.tqr_dgeqrt_host.argtypes = [_P, _P, _I, _I, _I, _I]
     L.tqr_sgeqrt_host.argtypes = [_P, _P, _I, _I, _I, _I]
+    L.tqr_flow_list_export.argtypes = [_P, _P, _I]
     L.tqr_apply_create.argtypes = [ctypes.POINTER(_P), _I, _I, _I, _I]
     L.tqr_apply_create.restype = _I
     L.tqr_apply_workspace_bytes.argtypes = [_P]
@@ -342,6 +343,25 @@ def dist_plan_check(M, N, b, rank, world, seglen=8):
     check(lib().tqr_dist_plan_check(M, N, b, seglen, rank, world, ctypes.byref(nt), ctypes.byref(nf)),
           "tqr_dist_plan_check")
     return nt.value, nf.value
+
+
+class FlowListSpec(ctypes.Structure):
+    """tqr_flow_list_spec, include/tqr.h"""
+    _fields_ = [(f, _I) for f in ("M", "N", "b", "dtype", "seglen", "world", "rank", "full", "nxc")] + \
+               [("tcol", ctypes.c_double)]
+
+
+def flow_list(M, N, b, dtype=TQR_F64, seglen=0, world=1, rank=-1, full=1, nxc=0, tcol=0.0):
+    """Host-only: the persistent engine's task list of a plan (tqr_flow_list_export) as an (n, 4)
+    int32 array of {type | strip << 8, l, m, k}; rank < 0: the global list."""
+    spec = FlowListSpec(M, N, b, dtype, seglen, world, rank, full, nxc, tcol)
+    n = lib().tqr_flow_list_export(ctypes.byref(spec), None, 0)
+    if n < 0:
+        check(n, "tqr_flow_list_export")
+    items = np.zeros((n, 4), dtype=np.int32)
+    if lib().tqr_flow_list_export(ctypes.byref(spec), _ptr(items), n) != n:
+        raise TQRError("tqr_flow_list_export: the list changed between two calls")
+    return items
 
 
 def fill_randzo(A, m, n, seed, ldda=None, stream=None, col0=0):

@@ -85,6 +85,21 @@ int tqr_flow_strip_width(void);
  * {type | strip << 8, l, m, k} (chains: type 4, l = i0 | i1 << 16, k = step | segment << 16);
  * returns the number of tasks (writes at most `cap`). */
 int tqr_flow_plan_export(int M, int N, int b, int seglen, int* items, int cap);
+/* Host-only: the task list of any plan, in the same 4-int form — exactly the list
+ * tqr_plan_create / tqr_dist_plan_create builds for the spec (nxc = 0), or the host-pointer API's
+ * list with nxc upload / download tasks per tile column (nxc 1..255, one-GPU plans only).
+ *   M, N    tiles;  dtype: tqr_dtype;  seglen <= 0: the plan's default segment length;
+ *   world   ranks, full != 0: each rank's launch covers its whole device (the multi-rank defaults
+ *           depend on both);  rank < 0: the global list, else that rank's partition of it;
+ *   tcol    with nxc > 0: one tile column's upload time in chain elements.
+ * The environment's task-list knobs apply as at plan creation. Returns the number of tasks
+ * (writes at most `cap`), or TQR_EINVAL. tqr_flow_plan_export and the *_plan_check functions
+ * are this call for fp64, full = 1 and a caller-given seglen >= 1. */
+typedef struct tqr_flow_list_spec {
+    int M, N, b, dtype, seglen, world, rank, full, nxc;
+    double tcol;
+} tqr_flow_list_spec;
+int tqr_flow_list_export(const tqr_flow_list_spec* spec, int* items, int cap);
 /* Replace the persistent engine's task order (the same tasks as the plan's list, 4 ints each as
  * tqr_flow_plan_export gives them, e.g. from an offline list scheduler): rejected with
  * TQR_EINVAL unless it is a permutation of the plan's tasks that is topological for every

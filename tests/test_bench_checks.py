@@ -153,7 +153,7 @@ def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
 
 
 def test_chain_segment_length_rule(monkeypatch):
-    """bench.seglen_of mirrors engine.hip env_seglen: 8 on one or two ranks, 2 from four ranks on
+    """bench.seglen_of mirrors flowplan.cpp env_seglen: 8 on one or two ranks, 2 from four ranks on
     (tools/sched_sim.py seglen), TQR_SEGLEN overrides."""
     monkeypatch.delenv("TQR_SEGLEN", raising=False)
     assert [bench.seglen_of(w) for w in (1, 2, 4, 8)] == [8, 8, 2, 2]

@@ -288,7 +288,7 @@ def test_task_order_and_lookahead_segments_bitexact(tqr):
             os.environ["TQR_SEGLEN_LA"] = old
     A2, t2 = run(p2)
     assert torch.equal(A0, A2) and torch.equal(t0, t2)
-    # the fp64 list's one-element tail segments (engine.hip default_tail; every step of this size)
+    # the fp64 list's one-element tail segments (flowplan.cpp default_tail; every step of this size)
     # against none (TQR_TAIL=0) and two-element ones
     for env in ({"TQR_TAIL": "0"}, {"TQR_TAIL_SEGLEN": "2"}):
         saved = {k: os.environ.get(k) for k in env}

@@ -24,11 +24,6 @@
 
 #include "gridscheduler.h"
 #include "tiles.hpp"
-namespace tqr {
-struct Item {  // (as engine.hip: flow.hpp, which chain32.hpp needs, names it)
-  int ts, l, m, k;
-};
-}  // namespace tqr
 #include "flow.hpp"
 
 using namespace tqr;

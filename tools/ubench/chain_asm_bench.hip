@@ -20,11 +20,6 @@
 #include <cstdlib>
 
 #include "gridscheduler.h"
-namespace tqr {
-struct Item {
-  int ts, l, m, k;
-};
-}  // namespace tqr
 #include "flow.hpp"
 
 using namespace tqr;

@@ -14,11 +14,6 @@
 #include <vector>
 
 #include "gridscheduler.h"
-namespace tqr {
-struct Item {
-  int ts, l, m, k;
-};
-}  // namespace tqr
 #include "flow.hpp"
 
 using namespace tqr;

@@ -14,7 +14,6 @@
 #include <vector>
 #include "tiles.hpp"
 #include "gridscheduler.h"
-namespace tqr { struct Item { int ts, l, m, k; }; }
 #include "flow.hpp"
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("HIP %s line %d\n", hipGetErrorString(e_), __LINE__); return 1; } } while (0)
 using namespace tqr;
