@@ -19,6 +19,7 @@
 #include <mutex>
 #include <new>
 
+#include "solve.hpp"
 #include "tiles.hpp"
 #include "tqr.h"
 
@@ -416,6 +417,33 @@ int tqr_apply_q(tqr_apply* ap, int trans, const void* dA, int ldda, void* dC, in
   ap->slotStream[slot] = cs;
   if (slot == ap->nslot) ap->nslot = slot + 1;
   return TQR_OK;
+}
+
+// Both gels directions on the handle's factorisation (include/tqr.h "solve"): the apply above and
+// solve.hip's tqr_trsm_r / resnorm enqueued on `stream`, nothing allocated. The solve reads dA
+// only (not the T workspace), so it needs none of the handle's events.
+int tqr_lstsq(tqr_apply* ap, int trans, const void* dA, int ldda, void* dB, int nrhs, int lddb, void* dres,
+              void* stream) {
+  if (!ap || !dA || !dB || nrhs < 1 || ap->m < ap->n || ldda < ap->m || lddb < ap->m || !apply_valid_ld(ldda, ap->es) ||
+      !apply_valid_ld(lddb, ap->es) || (trans != TQR_NOTRANS && trans != TQR_TRANS))
+    return TQR_EINVAL;
+  {
+    std::lock_guard<std::mutex> lk(ap->mu);
+    if (!ap->prepared) return TQR_EINVAL;
+  }
+  int st;
+  if (trans == TQR_NOTRANS) {
+    // B <- Q^T B; rows 0 .. n-1 <- R^{-1} of them; the residual norms from rows n .. m-1
+    if ((st = tqr_apply_q(ap, TQR_TRANS, dA, ldda, dB, nrhs, lddb, stream)) != TQR_OK) return st;
+    if ((st = tqr_trsm_r(ap->dtype, TQR_NOTRANS, ap->n, ap->b, dA, ldda, dB, nrhs, lddb, stream)) != TQR_OK) return st;
+    return dres ? resnorm(ap->dtype, dB, lddb, ap->n, ap->m, nrhs, dres, stream) : TQR_OK;
+  }
+  // x = Q [R^{-T} c; 0]
+  if (ap->m > ap->n)
+    HIPCHK(hipMemset2DAsync((char*)dB + (size_t)ap->n * ap->es, (size_t)lddb * ap->es, 0, (size_t)(ap->m - ap->n) * ap->es,
+                            (size_t)nrhs, (hipStream_t)stream));
+  if ((st = tqr_trsm_r(ap->dtype, TQR_TRANS, ap->n, ap->b, dA, ldda, dB, nrhs, lddb, stream)) != TQR_OK) return st;
+  return tqr_apply_q(ap, TQR_NOTRANS, dA, ldda, dB, nrhs, lddb, stream);
 }
 
 }  // extern "C"

@@ -1127,4 +1127,41 @@ __device__ __noinline__ void build_t(const double* Vs, const double* tauv, doubl
   BT_STAMP(3);
 }
 
+// ---------------------------------------------------------------------------------------
+// Z += V^T X over the k-steps ks_lo <= ks < ks_hi only (wave-uniform bounds): the first product of
+// apply_zw on its own, with no T and no W — the tile update of the triangular solve (solve.hip:
+// Z the target rows, V the negated operand image, X the solved strip). Operand reads one k-step
+// ahead and one scheduling region per k-step, as apply_zw; k-steps outside the range are neither
+// read into a product nor multiplied (an X row outside it may hold anything).
+// ---------------------------------------------------------------------------------------
+template <int B, int IBX = Geo<B>::IB>
+__device__ __forceinline__ void accum_z(const double* __restrict__ Vs, const double (&X)[Geo<B>::NKS],
+                                        double (&Z)[Geo<B, IBX>::NRI], int ks_lo, int ks_hi) {
+  using g = Geo<B, IBX>;
+  constexpr int NRI = g::NRI, NKS = g::NKS, VP = g::VP;
+  const int lane = threadIdx.x & 63, x = lane >> 4, y = lane & 3;
+  const unsigned vz = lds_base(Vs + x * VP + y * NRI);  // (see apply_zw)
+  auto ldz = [&](double (&a)[NRI], int ks) {
+#pragma unroll
+    for (int h = 0; h < NRI / 2; ++h) {
+      const d2v_t t = lds_rd2(vz + (unsigned)((4 * ks * VP + 2 * h) * sizeof(double)));
+      a[2 * h] = t.x;
+      a[2 * h + 1] = t.y;
+    }
+  };
+  double ac[NRI], an[NRI];
+  if (ks_lo < ks_hi) ldz(ac, ks_lo);
+#pragma unroll
+  for (int ks = 0; ks < NKS; ++ks) {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" ::: "memory");
+    if (ks < ks_lo || ks >= ks_hi) continue;
+    if (ks + 1 < NKS) ldz(an, ks + 1);
+#pragma unroll
+    for (int r = 0; r < NRI; ++r) Z[r] = mfma4(ac[r], X[ks], Z[r]);
+#pragma unroll
+    for (int r = 0; r < NRI; ++r) ac[r] = an[r];
+  }
+}
+
 }  // namespace tqr

@@ -99,6 +99,10 @@ def lib():
     L.tqr_apply_q.restype = _I
     L.tqr_apply_destroy.argtypes = [_P]
     L.tqr_apply_destroy.restype = None
+    L.tqr_trsm_r.argtypes = [_I, _I, _I, _I, _P, _I, _P, _I, _I, _P]
+    L.tqr_trsm_r.restype = _I
+    L.tqr_lstsq.argtypes = [_P, _I, _P, _I, _P, _I, _I, _P, _P]
+    L.tqr_lstsq.restype = _I
     _lib = L
     return L
 
@@ -446,12 +450,38 @@ class ApplyQ:
         check(lib().tqr_apply_q(self.h, 1 if trans else 0, _ptr(A), ldda, _ptr(C), nrhs, lddc, _stream_handle(stream)),
               "tqr_apply_q")
 
+    def lstsq(self, A, B, trans=False, nrhs=None, ldda=None, lddb=None, res=None, stream=None):
+        """tqr_lstsq on a prepared handle with m >= n; A as given to prepare(), B (nrhs, lddb) in place.
+        trans=False: least squares — B <- Q^T B, then rows 0 .. n-1 <- X; `res` (optional, nrhs
+        elements of B's dtype) receives |A x - b| per column. trans=True: the minimum-norm solution of
+        A^T x = c, c in rows 0 .. n-1 of B on entry, x in all m rows on exit. Stream-ordered."""
+        ldda = ldda or A.shape[-1]
+        lddb = lddb or B.shape[-1]
+        nrhs = B.shape[0] if nrhs is None else nrhs
+        check(lib().tqr_lstsq(self.h, 1 if trans else 0, _ptr(A), ldda, _ptr(B), nrhs, lddb,
+                              None if res is None else _ptr(res), _stream_handle(stream)), "tqr_lstsq")
+
     def __del__(self):
         try:
             if self.h:
                 lib().tqr_apply_destroy(self.h)
         except Exception:
             pass
+
+
+def trsm_r(F, X, b, trans=False, n=None, nrhs=None, ldda=None, lddx=None, stream=None):
+    """X <- R^{-1} X (or R^{-T} X with trans) in place, R the upper triangle of the leading n x n block
+    of the factorised F (tqr_trsm_r, include/tqr.h "solve"). F (>= n, ldda) and X (>= nrhs, lddx) are
+    device tensors of one dtype; n defaults to F's column count, nrhs, ldda and lddx to the tensors'
+    shapes. No handle and no workspace. Stream-ordered."""
+    if X.dtype != F.dtype:
+        raise TQRError("trsm_r: F and X must be of one dtype")
+    n = F.shape[0] if n is None else n
+    nrhs = X.shape[0] if nrhs is None else nrhs
+    ldda = ldda or F.shape[-1]
+    lddx = lddx or X.shape[-1]
+    check(lib().tqr_trsm_r(_dtype_code(F.dtype), 1 if trans else 0, n, b, _ptr(F), ldda, _ptr(X), nrhs, lddx,
+                           _stream_handle(stream)), "tqr_trsm_r")
 
 
 def lstsq(F, tau, B, b):

@@ -156,6 +156,46 @@ int tqr_apply_prepare(tqr_apply* ap, const void* dA, int ldda, const void* dtau_
 int tqr_apply_q(tqr_apply* ap, int trans, const void* dA, int ldda, void* dC, int nrhs, int lddc, void* stream);
 void tqr_apply_destroy(tqr_apply* ap);
 
+/* ---- solve: triangular solves with R, and both least-squares directions --------------------
+ * tqr_trsm_r: X <- R^{-1} X (TQR_NOTRANS) or X <- R^{-T} X (TQR_TRANS), in place, R = the upper
+ * triangle of the leading n x n block of dA as tqr_plan_execute left it. Only elements (i, j) with
+ * i <= j < n are read as values: everything below the diagonal of the diagonal tiles (the GEQRT V)
+ * is ignored, whatever it holds (it is masked by a select, so an inf or NaN there cannot leak). dA is
+ * not written. X is n x nrhs, column-major, of `dtype`, lddx >= n; nrhs >= 1 need not be a multiple
+ * of anything. Rows >= n and columns >= nrhs of X's allocation are not touched. b in {16, 32, 64,
+ * 128, 256} must divide n; ldda >= n and lddx obey the library's leading-dimension bound (above).
+ * No handle, no workspace, no prepare pass: the call is stream-ordered and returns once enqueued.
+ * Every argument error returns TQR_EINVAL before any device call; a missing or non-gfx950 device
+ * returns TQR_ENODEV after that validation.
+ * Method: one workgroup per 64 columns of X walks the tile rows of R serially (k descending for R,
+ * ascending for R^T); workgroups never wait for each other (the kernel has no counters or flags),
+ * so a narrow X uses few CUs. Inside a tile the 32 x 32 diagonal blocks are solved by substitution,
+ * dividing by R's own diagonal entries (no inverse is formed): the computed X satisfies the
+ * componentwise substitution bound |op(R) X - Y| <= gamma_n (|op(R)| |X| + |Y|).
+ * R is NOT checked for zero diagonal entries, and inf / NaN propagate as in BLAS trsm: a zero
+ * diagonal gives inf or NaN in the rows that depend on it. fp32 storage loads and stores float and
+ * computes in fp64; X is rounded to float whenever a tile row is stored.
+ *
+ * tqr_lstsq: LAPACK gels in both directions on a prepared apply handle with m >= n (else, or before
+ * the first prepare, TQR_EINVAL). dA / ldda as given to tqr_apply_prepare. Everything is enqueued on
+ * `stream`, nothing is allocated.
+ *   TQR_NOTRANS: least squares, min |A x - b|_2 for every column. dB (m x nrhs, lddb >= m) is
+ *                overwritten by Q^T B (tqr_apply_q), then rows 0 .. n-1 by X (tqr_trsm_r); rows
+ *                n .. m-1 stay exactly as the apply left them. dres: NULL, or nrhs elements of the
+ *                handle's dtype that receive |A x - b|_2 per column = the 2-norm of rows n .. m-1
+ *                (0 when m == n). The norm is accumulated in fp64 in a fixed order (bit-reproducible)
+ *                and is not scaled: squares of entries beyond about 1e154 in magnitude overflow to
+ *                inf and entries below about 1e-154 are lost (fp32 storage: the whole float range is
+ *                safe in the sum; a result beyond FLT_MAX rounds to inf).
+ *   TQR_TRANS:   the minimum-norm solution of the underdetermined A^T x = c. On entry rows 0 .. n-1
+ *                of dB hold c; rows n .. m-1 are ignored and zeroed by the call. Rows 0 .. n-1 become
+ *                R^{-T} c (tqr_trsm_r), then dB <- Q dB (tqr_apply_q): on exit all m rows hold x.
+ *                dres is not written. */
+int tqr_trsm_r(int dtype, int trans, int n, int b, const void* dA, int ldda, void* dX, int nrhs, int lddx,
+               void* stream);
+int tqr_lstsq(tqr_apply* ap, int trans, const void* dA, int ldda, void* dB, int nrhs, int lddb, void* dres,
+              void* stream);
+
 /* ---- multi-GPU: tile-column partition, one process per GPU ---------------------------------
  * Rank r owns the tile columns j with tqr_dist_owner(j) == r — snake order over the ranks
  * (0..W-1, W-1..0, 0..W-1, ...: every rank's columns sum to the same index total, balancing the
