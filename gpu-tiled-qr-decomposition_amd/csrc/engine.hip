@@ -33,6 +33,7 @@
 
 #include "flowplan.hpp"
 #include "gridscheduler.h"
+#include "solve.hpp"
 #include "tiles.hpp"
 #include "tqr.h"
 
@@ -437,6 +438,7 @@ struct tqr_plan {
   int chain_asm = 2;  // fp64 chains on the hand-scheduled MFMA stream (TQR_CHAIN_ASM: 0 compiler-scheduled, 1 whole strip loaded in the hand-over, 2 late strip loads)
   // flow engine
   int engine = 1;          // 1 = persistent dataflow (default), 0 = wave-batched launches
+  bool capped = false;     // tqr_plan_create_steps: kmax is the caller's cap (flow engine, one GPU, device pointers)
   Item* d_flow = nullptr;
   int nflow = 0;
   int nflow_global = 0;  // tasks of the global list (before a multi-GPU partition)
@@ -482,6 +484,9 @@ struct tqr_plan {
   hipStream_t sC = nullptr;
   hipEvent_t pev[2] = {nullptr, nullptr};
 };
+
+// what solve.hip's tqr_lstsq_fused reads of a plan (solve.hpp)
+tqr::PlanShape tqr::plan_shape(const tqr_plan* pl) { return PlanShape{pl->m, pl->n, pl->b, pl->dtype, pl->kmax, pl->capped}; }
 
 // transfer arguments of one host-pointer execute of the flow engine (xfer.hpp)
 struct XferArgs {
@@ -569,7 +574,7 @@ void tqr_plan_destroy(tqr_plan* pl) {
   delete pl;
 }
 
-static int plan_create(tqr_plan** out, int m, int n, int b, int dtype, int rank, int world, int engine);
+static int plan_create(tqr_plan** out, int m, int n, int b, int dtype, int rank, int world, int engine, int steps = 0);
 int tqr_plan_create(tqr_plan** out, int m, int n, int b, int dtype) {
   return plan_create(out, m, n, b, dtype, 0, 1, TQR_ENGINE_DEFAULT);
 }
@@ -616,7 +621,17 @@ int tqr_dist_plan_create(tqr_plan** out, int m, int n, int b, int dtype, int ran
   if (world < 1 || rank < 0 || rank >= world) return TQR_EINVAL;
   return plan_create(out, m, n, b, dtype, rank, world, TQR_ENGINE_FLOW);
 }
-static int plan_create(tqr_plan** out, int m, int n, int b, int dtype, int rank, int world, int engine) {
+// A capped plan (include/tqr.h): panels for the leading `steps` tile columns only. Always the flow
+// engine — the wave engine replays sched.c's waves of the whole DAG.
+int tqr_plan_create_steps(tqr_plan** out, int m, int n, int b, int dtype, int steps) {
+  if (!out) return TQR_EINVAL;
+  *out = nullptr;
+  if (!valid_b(b) || m <= 0 || n <= 0 || steps < 1 || steps > std::min(m, n) / b) return TQR_EINVAL;
+  return plan_create(out, m, n, b, dtype, 0, 1, TQR_ENGINE_FLOW, steps);
+}
+int tqr_plan_steps(const tqr_plan* pl) { return pl ? pl->kmax : TQR_EINVAL; }
+// steps > 0: tqr_plan_create_steps's cap (already checked against min(m, n) / b)
+static int plan_create(tqr_plan** out, int m, int n, int b, int dtype, int rank, int world, int engine, int steps) {
   if (!out) return TQR_EINVAL;
   *out = nullptr;
   if (!valid_b(b) || m <= 0 || n <= 0 || m % b || n % b || (dtype != TQR_F32 && dtype != TQR_F64) ||
@@ -628,7 +643,8 @@ static int plan_create(tqr_plan** out, int m, int n, int b, int dtype, int rank,
   if (!pl) return TQR_ENOMEM;
   pl->m = m; pl->n = n; pl->b = b; pl->p = m / b; pl->q = n / b;
   pl->rank = rank; pl->world = world; pl->cyclic = world > 1 && dist_cyclic();
-  pl->kmax = std::min(pl->p, pl->q);
+  pl->capped = steps > 0;
+  pl->kmax = flow_kmax(pl->p, pl->q, steps);
   pl->dtype = dtype;
   pl->es = dtype == TQR_F64 ? 8 : 4;
 
@@ -704,13 +720,13 @@ static int plan_create(tqr_plan** out, int m, int n, int b, int dtype, int rank,
     pl->grid = full_grid;
     if (const char* gs = getenv("TQR_FLOW_GRID")) pl->grid = std::max(1, atoi(gs));
     FlowPlan fp;
-    pl->knobs = flow_knobs(pl->p, pl->q, dtype, world, pl->grid >= full_grid, 0);
+    pl->knobs = flow_knobs(pl->p, pl->q, dtype, world, pl->grid >= full_grid, 0, steps);
     if (const char* eca = getenv("TQR_CHAIN_ASM")) pl->chain_asm = atoi(eca) & 3;  // 0 off, 1 on, 2 late strip loads
     // (bit 2: UNMQR elements on the full TSMQR bodies instead of the zero-row-skipping ones; A/B only)
     if (const char* eu = getenv("TQR_UNMQR_SKIP"); eu && atoi(eu) == 0 && pl->chain_asm) pl->chain_asm |= 4;
     // (bit 3: fp32 storage on the compiler-scheduled flow_chain32; A/B only)
     if (const char* e32 = getenv("TQR_CHAIN32_ASM"); e32 && atoi(e32) == 0) pl->chain_asm |= 8;
-    build_flow_plan(pl->p, pl->q, pl->ns, pl->ng, pl->knobs, fp);
+    build_flow_plan(pl->p, pl->q, pl->ns, pl->ng, pl->knobs, fp, nullptr, steps);
     pl->nflow_global = (int)fp.items.size();
     pl->list_hash = flow_list_hash(fp.items);  // of the global list: the ranks must agree on it (tqr_dist_import)
     if (world > 1) partition_flow_plan(fp, rank, world);
@@ -962,7 +978,7 @@ int tqr_dist_reset(tqr_plan* pl, void* stream) {
 }
 
 int tqr_dist_local_cols(const tqr_plan* pl) {
-  if (!pl) return TQR_EINVAL;
+  if (!pl || pl->capped) return TQR_EINVAL;
   int c = 0;
   for (int j = 0; j < pl->q; ++j) c += tile_owner(j, pl->world, pl->cyclic) == pl->rank;
   return c;
@@ -979,7 +995,7 @@ long long tqr_plan_fwd_bytes(const tqr_plan* pl) {
 }
 
 int tqr_dist_owner(const tqr_plan* pl, int tile_col) {
-  if (!pl || tile_col < 0 || tile_col >= pl->q) return TQR_EINVAL;
+  if (!pl || pl->capped || tile_col < 0 || tile_col >= pl->q) return TQR_EINVAL;
   return tile_owner(tile_col, pl->world, pl->cyclic);
 }
 

@@ -112,8 +112,7 @@ bool flow_list_topological(const std::vector<Item>& L, int p, int q, int ns) {
 // add a head load and store per element there: no gain at 16-32 steps of 128, slower beyond
 // (48: +2.3 ms) — off for fp32. Tall matrices (65536 x 16384) never reach the tail rows.
 constexpr int kTailRows = 31;
-static int default_tail(int p, int q, int dtype) {
-  const int kmax = std::min(p, q);
+static int default_tail(int p, int kmax, int dtype) {
   if (dtype != TQR_F64) return 0;
   return std::max(0, std::min(kmax, kmax - (p - 1 - kTailRows)));
 }
@@ -143,13 +142,12 @@ struct MultiRankDefaults {
   double lac;   // < 0: the panel keying (TQR_LA's default)
   int ualone;   // < 0: follow the tail
 };
-static MultiRankDefaults multi_rank_defaults(int p, int q, int dtype, int world, bool full) {
-  const int kmax = std::min(p, q);
+static MultiRankDefaults multi_rank_defaults(int p, int kmax, int dtype, int world, bool full) {
   const char* e = getenv("TQR_DIST_DEFAULTS");
   const bool r4 = e && std::string(e) == "r4";
-  if (world >= 4 && full && !r4) return {std::max(default_tail(p, q, dtype), 7 * kmax / 16), 4.0, 0};
-  if (world > 1) return {default_tail(p, q, dtype), -1.0, 0};
-  return {default_tail(p, q, dtype), -1.0, -1};
+  if (world >= 4 && full && !r4) return {std::max(default_tail(p, kmax, dtype), 7 * kmax / 16), 4.0, 0};
+  if (world > 1) return {default_tail(p, kmax, dtype), -1.0, 0};
+  return {default_tail(p, kmax, dtype), -1.0, -1};
 }
 static FlowKnobs knobs_from_env(int seglen, int tail_default, double la_default, double lac_default, int ualone_default) {
   FlowKnobs kn;
@@ -184,13 +182,13 @@ static int env_seglen(int world, bool full) {
   const char* sl = getenv("TQR_SEGLEN");
   return sl ? std::max(1, atoi(sl)) : (world >= 4 && full ? 2 : 8);
 }
-FlowKnobs flow_knobs(int p, int q, int dtype, int world, bool full, int seglen) {
-  const MultiRankDefaults mrd = multi_rank_defaults(p, q, dtype, world, full);
+FlowKnobs flow_knobs(int p, int q, int dtype, int world, bool full, int seglen, int steps) {
+  const MultiRankDefaults mrd = multi_rank_defaults(p, flow_kmax(p, q, steps), dtype, world, full);
   return knobs_from_env(seglen > 0 ? seglen : env_seglen(world, full), mrd.tail, default_la(dtype), mrd.lac, mrd.ualone);
 }
 
-void build_flow_plan(int p, int q, int ns, int ng, const FlowKnobs& kn, FlowPlan& fp, const XferPlan* xp) {
-  const int kmax = std::min(p, q);
+void build_flow_plan(int p, int q, int ns, int ng, const FlowKnobs& kn, FlowPlan& fp, const XferPlan* xp, int steps) {
+  const int kmax = flow_kmax(p, q, steps);
   // segment length per chain: shorter segments for the lookahead column pipeline consecutive
   // elements on different workgroups at reflector-group granularity
   auto seglen_of = [&](int k, int j) { return seglen_of_chain(k, j, kmax, kn.seglen, kn.seglen_la, kn.la_tail, kn.tail, kn.tail_sl); };
@@ -369,7 +367,8 @@ unsigned flow_list_hash(const std::vector<Item>& L) {
   return h;
 }
 
-int flow_list(const tqr_flow_list_spec& sp, FlowPlan& fp) {
+int flow_list(const tqr_flow_list_spec& sp, FlowPlan& fp, int steps) {
+  if (steps > 0 && (steps > std::min(sp.M, sp.N) || sp.world != 1 || sp.nxc != 0)) return TQR_EINVAL;  // capped: one-GPU device lists
   if (sp.M <= 0 || sp.N <= 0 || !valid_b(sp.b) || (sp.dtype != TQR_F32 && sp.dtype != TQR_F64) || sp.world < 1 ||
       sp.rank >= sp.world || sp.nxc < 0 || sp.nxc > 255 || !(sp.tcol >= 0.0) || (sp.nxc > 0 && sp.world > 1))
     return TQR_EINVAL;
@@ -378,7 +377,7 @@ int flow_list(const tqr_flow_list_spec& sp, FlowPlan& fp) {
   xp.nxc = sp.nxc;
   xp.tcol = sp.tcol;
   build_flow_plan(sp.M, sp.N, shape_ns(sh, sp.b), sp.b / shape_ib(sh, sp.b),
-                  flow_knobs(sp.M, sp.N, sp.dtype, sp.world, sp.full != 0, sp.seglen), fp, sp.nxc > 0 ? &xp : nullptr);
+                  flow_knobs(sp.M, sp.N, sp.dtype, sp.world, sp.full != 0, sp.seglen, steps), fp, sp.nxc > 0 ? &xp : nullptr, steps);
   if (sp.world > 1 && sp.rank >= 0) partition_flow_plan(fp, sp.rank, sp.world);
   return TQR_OK;
 }
@@ -402,9 +401,9 @@ static int list_check(const tqr_flow_list_spec& sp, int* ntasks, int* est_order)
 
 extern "C" {
 
-int tqr_flow_list_export(const tqr_flow_list_spec* spec, int* items, int cap) {
+int tqr_flow_list_export_steps(const tqr_flow_list_spec* spec, int steps, int* items, int cap) {
   FlowPlan fp;
-  if (!spec || flow_list(*spec, fp) != TQR_OK) return TQR_EINVAL;
+  if (!spec || flow_list(*spec, fp, std::max(0, steps)) != TQR_OK) return TQR_EINVAL;
   const int n = (int)fp.items.size();
   if (items)
     for (int x = 0; x < n && x < cap; ++x) {
@@ -412,6 +411,10 @@ int tqr_flow_list_export(const tqr_flow_list_spec* spec, int* items, int cap) {
       items[4 * x + 2] = fp.items[x].m; items[4 * x + 3] = fp.items[x].k;
     }
   return n;
+}
+
+int tqr_flow_list_export(const tqr_flow_list_spec* spec, int* items, int cap) {
+  return tqr_flow_list_export_steps(spec, 0, items, cap);
 }
 
 int tqr_flow_plan_export(int M, int N, int b, int seglen, int* items, int cap) {

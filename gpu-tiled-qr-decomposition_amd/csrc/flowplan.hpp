@@ -76,11 +76,17 @@ struct FlowKnobs {
 // rank's launch covers its whole device — every rank must decide alike, tqr_dist_import checks the
 // ranks' task-list signatures), then the environment's overrides. seglen <= 0: the default
 // (TQR_SEGLEN, else by world and full); a positive value is used as it is.
-FlowKnobs flow_knobs(int p, int q, int dtype, int world, bool full, int seglen);
+// steps > 0: a capped plan (tqr_plan_create_steps) — the defaults that count steps back from the last
+// one (tail, ualone, the multi-rank tail) count back from step steps - 1.
+FlowKnobs flow_knobs(int p, int q, int dtype, int world, bool full, int seglen, int steps = 0);
+// Steps of a plan of p x q tiles: min(p, q), or the cap of a capped plan (1 <= steps <= min(p, q):
+// only the leading `steps` tile columns get panels, every other column only their chains).
+inline int flow_kmax(int p, int q, int steps) { return steps > 0 ? std::min(steps, std::min(p, q)) : std::min(p, q); }
 
 // ns: chain strips per tile column, ng: reflector groups per tile (the engine shape's, shape_ns /
-// b / shape_ib)
-void build_flow_plan(int p, int q, int ns, int ng, const FlowKnobs& kn, FlowPlan& fp, const XferPlan* xp = nullptr);
+// b / shape_ib); steps: the cap (0: none), which must be the one the knobs were made for
+void build_flow_plan(int p, int q, int ns, int ng, const FlowKnobs& kn, FlowPlan& fp, const XferPlan* xp = nullptr,
+                     int steps = 0);
 // TQR_DIST_PART=cyclic: the round-2 partition j % world (A/B diagnostics; default snake)
 int dist_cyclic();
 void partition_flow_plan(FlowPlan& fp, int rank, int world);
@@ -89,7 +95,8 @@ bool flow_list_topological(const std::vector<Item>& L, int p, int q, int ns);
 // segments, lookahead keys, TQR_LA / LAC / TG / LAZY — must agree across the ranks, tqr_dist_import)
 unsigned flow_list_hash(const std::vector<Item>& L);
 // The list of a spec (tqr.h tqr_flow_list_spec): what plan_create (nxc = 0) or plan_xfer_list
-// builds for it. TQR_OK or TQR_EINVAL.
-int flow_list(const tqr_flow_list_spec& sp, FlowPlan& fp);
+// builds for it, or with steps > 0 what tqr_plan_create_steps builds (world 1, nxc 0, steps <=
+// min(M, N), else TQR_EINVAL). TQR_OK or TQR_EINVAL.
+int flow_list(const tqr_flow_list_spec& sp, FlowPlan& fp, int steps = 0);
 
 }  // namespace tqr

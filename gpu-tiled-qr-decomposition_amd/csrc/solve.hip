@@ -8,6 +8,7 @@
 //                X_k, then subtracts R_ik X_k (R: i < k) or R_ki^T X_k (R^T: i > k) from every other
 //                tile row still to be solved.
 //   resnorm      k_resnorm: the 2-norm of rows n .. m-1 of every column of Q^T B.
+//   tqr_lstsq_fused  host only: a capped plan's execute over [A | B], then the two above on B.
 // R is read where the factorisation left it: the GEQRT V below the diagonal of the diagonal tiles
 // is replaced by zeros with a select while the tile is staged, and never enters a product.
 // The column strips of X are independent, so workgroups never communicate: the only
@@ -360,6 +361,23 @@ int tqr_trsm_r(int dtype, int trans, int n, int b, const void* dA, int ldda, voi
   hipLaunchKernelGGL(fn, dim3(grid), dim3(NT), lds_solve(b), (hipStream_t)stream, a);
   HIPCHK(hipGetLastError());
   return TQR_OK;
+}
+
+// Least squares in one factorisation launch (include/tqr.h "solve"): the capped plan over [A | B]
+// leaves Q^T B in B's place (the engine's chains, pipelined over the steps), so what remains is the
+// solve with R and the residual norms — tqr_lstsq's own last two steps, on B's columns inside dAB.
+int tqr_lstsq_fused(tqr_plan* plan, void* dAB, int ldda, void* dtau, int nrhs, void* dres, void* stream) {
+  if (!plan || !dAB || !dtau) return TQR_EINVAL;
+  const PlanShape ps = plan_shape(plan);
+  const int n = ps.steps * ps.b;  // A's columns; B's tile columns follow
+  if (!ps.capped || n >= ps.n || ps.m < n || nrhs < 1 || nrhs > ps.n - n || ldda < ps.m ||
+      !solve_valid_ld(ldda, ps.dtype == TQR_F64 ? 8 : 4))
+    return TQR_EINVAL;
+  void* dB = (char*)dAB + (size_t)n * (size_t)ldda * (ps.dtype == TQR_F64 ? 8 : 4);
+  int st;
+  if ((st = tqr_plan_execute(plan, dAB, ldda, dtau, stream)) != TQR_OK) return st;
+  if ((st = tqr_trsm_r(ps.dtype, TQR_NOTRANS, n, ps.b, dAB, ldda, dB, nrhs, ldda, stream)) != TQR_OK) return st;
+  return dres ? resnorm(ps.dtype, dB, ldda, n, ps.m, nrhs, dres, stream) : TQR_OK;
 }
 
 }  // extern "C"

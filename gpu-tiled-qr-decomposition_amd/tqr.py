@@ -67,6 +67,10 @@ def lib():
     L.tqr_sched_total_tasks.restype = ctypes.c_long
     L.initScheduler.restype = ctypes.POINTER(Task)
     L.tqr_plan_create.argtypes = [ctypes.POINTER(_P), _I, _I, _I, _I]
+    L.tqr_plan_create_steps.argtypes = [ctypes.POINTER(_P), _I, _I, _I, _I, _I]
+    L.tqr_plan_create_steps.restype = _I
+    L.tqr_plan_steps.argtypes = [_P]
+    L.tqr_plan_steps.restype = _I
     L.tqr_plan_execute.argtypes = [_P, _P, _I, _P, _P]
     L.tqr_plan_destroy.argtypes = [_P]
     L.tqr_plan_set_profile.argtypes = [_P, _I]
@@ -89,6 +93,8 @@ def lib():
     L.tqr_dgeqrt_host.argtypes = [_P, _P, _I, _I, _I, _I]
     L.tqr_sgeqrt_host.argtypes = [_P, _P, _I, _I, _I, _I]
     L.tqr_flow_list_export.argtypes = [_P, _P, _I]
+    L.tqr_flow_list_export_steps.argtypes = [_P, _I, _P, _I]
+    L.tqr_flow_list_export_steps.restype = _I
     L.tqr_apply_create.argtypes = [ctypes.POINTER(_P), _I, _I, _I, _I]
     L.tqr_apply_create.restype = _I
     L.tqr_apply_workspace_bytes.argtypes = [_P]
@@ -103,6 +109,8 @@ def lib():
     L.tqr_trsm_r.restype = _I
     L.tqr_lstsq.argtypes = [_P, _I, _P, _I, _P, _I, _I, _P, _P]
     L.tqr_lstsq.restype = _I
+    L.tqr_lstsq_fused.argtypes = [_P, _P, _I, _P, _I, _P, _P]
+    L.tqr_lstsq_fused.restype = _I
     _lib = L
     return L
 
@@ -164,14 +172,21 @@ def sched_plan(M, N):
 
 # ---- device factorisation -------------------------------------------------------------------
 class TiledQR:
-    """A planned factorisation (tqr_plan): create once, execute on device arrays."""
+    """A planned factorisation (tqr_plan): create once, execute on device arrays. steps: a capped
+    plan (tqr_plan_create_steps) — only the leading `steps` tile columns are factorised, every other
+    column receives Q^T of those steps; tau is then (steps, m)."""
 
-    def __init__(self, m, n, b, dtype):
+    def __init__(self, m, n, b, dtype, steps=None):
         self.m, self.n, self.b = m, n, b
         self.dtype = dtype if isinstance(dtype, int) else _dtype_code(dtype)
-        self.kmax = min(m, n) // b
+        self.h = None
         h = _P()
-        check(lib().tqr_plan_create(ctypes.byref(h), m, n, b, self.dtype), "tqr_plan_create")
+        if steps is None:
+            self.kmax = min(m, n) // b
+            check(lib().tqr_plan_create(ctypes.byref(h), m, n, b, self.dtype), "tqr_plan_create")
+        else:
+            self.kmax = steps
+            check(lib().tqr_plan_create_steps(ctypes.byref(h), m, n, b, self.dtype, steps), "tqr_plan_create_steps")
         self.h = h
 
     def execute(self, A, tau, ldda=None, stream=None):
@@ -182,6 +197,13 @@ class TiledQR:
     def status(self, stream=None):
         """Synchronise `stream` and raise if the engine reported an error (tqr_plan_status)."""
         check(lib().tqr_plan_status(self.h, _P(stream or 0)), "tqr_plan_status")
+
+    def lstsq_fused(self, AB, tau, nrhs, res=None, ldda=None, stream=None):
+        """tqr_lstsq_fused on a capped plan over [A | B] (steps = A's tile columns): AB (n, ldda) in
+        place, tau (steps, m); `res` (optional) receives the nrhs residual norms. Stream-ordered."""
+        ldda = ldda or self.m
+        check(lib().tqr_lstsq_fused(self.h, _ptr(AB), ldda, _ptr(tau), nrhs, None if res is None else _ptr(res),
+                                    _stream_handle(stream)), "tqr_lstsq_fused")
 
     def set_profile(self, on=True):
         check(lib().tqr_plan_set_profile(self.h, int(on)))
@@ -194,7 +216,8 @@ class TiledQR:
 
     def __del__(self):
         try:
-            lib().tqr_plan_destroy(self.h)
+            if self.h:
+                lib().tqr_plan_destroy(self.h)
         except Exception:
             pass
 
@@ -355,15 +378,22 @@ class FlowListSpec(ctypes.Structure):
                [("tcol", ctypes.c_double)]
 
 
-def flow_list(M, N, b, dtype=TQR_F64, seglen=0, world=1, rank=-1, full=1, nxc=0, tcol=0.0):
+def flow_list(M, N, b, dtype=TQR_F64, seglen=0, world=1, rank=-1, full=1, nxc=0, tcol=0.0, steps=0):
     """Host-only: the persistent engine's task list of a plan (tqr_flow_list_export) as an (n, 4)
-    int32 array of {type | strip << 8, l, m, k}; rank < 0: the global list."""
+    int32 array of {type | strip << 8, l, m, k}; rank < 0: the global list. steps > 0: the list of a
+    capped plan (tqr_flow_list_export_steps)."""
     spec = FlowListSpec(M, N, b, dtype, seglen, world, rank, full, nxc, tcol)
-    n = lib().tqr_flow_list_export(ctypes.byref(spec), None, 0)
+    if steps:
+        def export(items, cap):
+            return lib().tqr_flow_list_export_steps(ctypes.byref(spec), steps, items, cap)
+    else:
+        def export(items, cap):
+            return lib().tqr_flow_list_export(ctypes.byref(spec), items, cap)
+    n = export(None, 0)
     if n < 0:
         check(n, "tqr_flow_list_export")
     items = np.zeros((n, 4), dtype=np.int32)
-    if lib().tqr_flow_list_export(ctypes.byref(spec), _ptr(items), n) != n:
+    if export(_ptr(items), n) != n:
         raise TQRError("tqr_flow_list_export: the list changed between two calls")
     return items
 
@@ -506,6 +536,53 @@ def lstsq(F, tau, B, b):
     X = torch.linalg.solve_triangular(Rt, B[:, :n], upper=False, left=False)
     res = torch.linalg.vector_norm(B[:, n:], dim=1)
     return X, res
+
+
+def lstsq_fused(A, B, b):
+    """Least squares min |A x - b| for every column of B with the factorisation itself, in one
+    pipelined launch (tqr_lstsq_fused, include/tqr.h): A (n, m) and B (nrhs, m) are device tensors of
+    one dtype, m >= n (row j = column j, as everywhere in this module). Builds [A | B padded with zero
+    columns to whole tiles], runs a capped plan over it, and returns (X (nrhs, n), res (nrhs,), F, tau):
+    F (n, m) and tau (n / b, m) are an ordinary factorisation of A — ApplyQ(m, n).prepare(F, tau) and
+    trsm_r(F, ...) work on them. A and B are not modified."""
+    import torch
+    n, m = A.shape
+    if m < n:
+        raise TQRError(f"lstsq_fused needs m >= n, got {m} x {n}")
+    if B.ndim != 2 or B.shape[-1] != m or B.dtype != A.dtype or B.shape[0] < 1:
+        raise TQRError("lstsq_fused: B must be (nrhs, m) of A's dtype")
+    nrhs = B.shape[0]
+    r = (nrhs + b - 1) // b
+    AB = torch.zeros((n + r * b, m), dtype=A.dtype, device=A.device)
+    AB[:n] = A
+    AB[n:n + nrhs] = B
+    plan = TiledQR(m, n + r * b, b, A.dtype, steps=n // b if b > 0 and n % b == 0 else 0)
+    tau = torch.zeros((n // b, m), dtype=A.dtype, device=A.device)
+    res = torch.empty((nrhs,), dtype=A.dtype, device=A.device)
+    cs = torch.cuda.current_stream()
+    plan.lstsq_fused(AB, tau, nrhs, res=res, stream=cs)
+    plan.status(cs.cuda_stream)
+    return AB[n:n + nrhs, :n], res, AB[:n], tau
+
+
+def form_qt(A, b):
+    """Q^T (m x m) of the tiled factorisation of A (n, m), m >= n, from a capped plan over [A | I]:
+    the identity's columns receive Q^T in the factorisation's own launch. Returns (Qt, F, tau): Qt
+    (m, m) with row j = column j of Q^T (so Qt.T, read in this module's convention, is Q), F (n, m)
+    and tau (n / b, m) an ordinary factorisation of A."""
+    import torch
+    n, m = A.shape
+    if m < n:
+        raise TQRError(f"form_qt needs m >= n, got {m} x {n}")
+    AI = torch.zeros((n + m, m), dtype=A.dtype, device=A.device)
+    AI[:n] = A
+    AI[n:].fill_diagonal_(1.0)
+    plan = TiledQR(m, n + m, b, A.dtype, steps=n // b if b > 0 and n % b == 0 else 0)
+    tau = torch.zeros((n // b, m), dtype=A.dtype, device=A.device)
+    cs = torch.cuda.current_stream()
+    plan.execute(AI, tau, stream=cs.cuda_stream)
+    plan.status(cs.cuda_stream)
+    return AI[n:], AI[:n], tau
 
 
 def apply_q_host(F, T, C, b, trans=True):

@@ -56,6 +56,28 @@ int tqr_plan_create(tqr_plan** plan, int m, int n, int b, int dtype);
  * TQR_ENGINE_DEFAULT = FLOW unless the environment sets TQR_ENGINE=waves. */
 enum tqr_engine { TQR_ENGINE_DEFAULT = -1, TQR_ENGINE_WAVES = 0, TQR_ENGINE_FLOW = 1 };
 int tqr_plan_create_engine(tqr_plan** plan, int m, int n, int b, int dtype, int engine);
+/* Partial factorisation ("capped plan"): factorise only the leading `steps` tile columns of the
+ * m x n matrix (1 <= steps <= min(m,n)/b, else TQR_EINVAL) and apply Q^T of those steps to every
+ * other column. On exit of tqr_plan_execute, with s = steps:
+ *   * columns 0 .. s*b-1 hold R, the GEQRT V and the TSQRT V_B of steps 0 .. s-1, as a whole
+ *     factorisation leaves them: they are a complete factorisation of the m x s*b matrix A[:, :s*b],
+ *     on which tqr_apply_*, tqr_trsm_r and tqr_lstsq work unchanged;
+ *   * rows 0 .. s*b-1 of the columns >= s*b hold R12 (final);
+ *   * rows >= s*b of the columns >= s*b hold the updated trailing block — the lower rows of
+ *     Q_s^T A[:, s*b:], no reflectors: the block-elimination form [R11 R12; 0 S]. An ordinary plan
+ *     of (m - s*b) x (n - s*b) executed in place on S (base pointer offset, same ldda, its own tau
+ *     array) completes the factorisation;
+ *   * dtau_compact is m x s: columns 0 .. s-1 of the usual compact layout.
+ * So a capped plan over [A | B] (steps = A's tile columns) factorises A and leaves Q^T B in B's
+ * place, and one over [A | I] leaves Q^T explicitly, both in the one pipelined launch.
+ * The plan always runs the persistent dataflow engine, whatever TQR_ENGINE says, and is a
+ * single-GPU device-pointer plan: every tqr_dist_* call on it returns TQR_EINVAL. Arguments are
+ * validated as by tqr_plan_create, before any device call. With steps == min(m,n)/b the task list
+ * is exactly tqr_plan_create's. tqr_plan_set_tasks, tqr_plan_info and tqr_plan_debug_workspace
+ * (k < steps) work on the capped plan's own list. */
+int tqr_plan_create_steps(tqr_plan** plan, int m, int n, int b, int dtype, int steps);
+/* The steps of a plan: the cap of a tqr_plan_create_steps plan, min(m,n)/b for every other plan. */
+int tqr_plan_steps(const tqr_plan* plan);
 void tqr_plan_destroy(tqr_plan* plan);
 
 /* Factorise device matrix dA (ldda >= m) in place; dtau_compact is device memory of
@@ -100,6 +122,10 @@ typedef struct tqr_flow_list_spec {
     double tcol;
 } tqr_flow_list_spec;
 int tqr_flow_list_export(const tqr_flow_list_spec* spec, int* items, int cap);
+/* The same for a capped plan (tqr_plan_create_steps of M*b x N*b with `steps`): exactly the list
+ * that plan builds. steps <= 0: uncapped, identical to tqr_flow_list_export. A capped spec must have
+ * world == 1, nxc == 0 and steps <= min(M, N), else TQR_EINVAL. */
+int tqr_flow_list_export_steps(const tqr_flow_list_spec* spec, int steps, int* items, int cap);
 /* Replace the persistent engine's task order (the same tasks as the plan's list, 4 ints each as
  * tqr_flow_plan_export gives them, e.g. from an offline list scheduler): rejected with
  * TQR_EINVAL unless it is a permutation of the plan's tasks that is topological for every
@@ -195,6 +221,23 @@ int tqr_trsm_r(int dtype, int trans, int n, int b, const void* dA, int ldda, voi
                void* stream);
 int tqr_lstsq(tqr_apply* ap, int trans, const void* dA, int ldda, void* dB, int nrhs, int lddb, void* dres,
               void* stream);
+/* tqr_lstsq_fused: least squares min |A x - b|_2 with the factorisation itself, in one stream-ordered
+ * call and no apply handle. plan = tqr_plan_create_steps(m, n + r*b, b, dtype, n/b) with m >= n and
+ * r >= 1; dAB (ldda >= m) holds [A | B]: A's n columns, then r tile columns of which the first nrhs
+ * (1 <= nrhs <= r*b) are the right-hand sides. The call enqueues tqr_plan_execute (which factorises
+ * A and leaves Q^T B in B's place), then tqr_trsm_r(TQR_NOTRANS) on rows 0 .. n-1 of B's nrhs
+ * columns, then — dres: NULL, or nrhs elements of the plan's dtype — |A x - b|_2 per column from
+ * rows n .. m-1, exactly as tqr_lstsq computes it (the same kernel, the same fixed summation order).
+ * On exit: columns 0 .. n-1 and dtau_compact (m x n/b) are an ordinary factorisation of A (an apply
+ * handle for (m, n) can be prepared on them); rows 0 .. n-1 of B's first nrhs columns hold X, their
+ * rows n .. m-1 the rest of Q^T B. The padding columns nrhs .. r*b-1 are OVERWRITTEN: they are
+ * updated like any column (by Q^T, not solved); columns are independent, so what they hold on entry
+ * influences nothing else — they need not be initialised to anything in particular, but inf / NaN in
+ * them stay in them. Nothing beyond the n + r*b columns is touched.
+ * Everything is validated before any device call (TQR_EINVAL): a NULL plan, dAB or dtau_compact; a
+ * plan not made by tqr_plan_create_steps; a plan without columns after its steps*b (no B); nrhs < 1
+ * or nrhs > r*b; a bad ldda. Status of the launch: tqr_plan_status, as after tqr_plan_execute. */
+int tqr_lstsq_fused(tqr_plan* plan, void* dAB, int ldda, void* dtau_compact, int nrhs, void* dres, void* stream);
 
 /* ---- multi-GPU: tile-column partition, one process per GPU ---------------------------------
  * Rank r owns the tile columns j with tqr_dist_owner(j) == r — snake order over the ranks
