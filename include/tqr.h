@@ -149,8 +149,12 @@ long tqr_total_tasks(int m, int n, int b);
 
 /* ---- apply: C <- Q^T C or C <- Q C with the factors of a finished factorisation -------------
  * (the ormqr to the plan's geqrf). dA, ldda and dtau_compact are what tqr_plan_execute left on the
- * device: R, the V tiles and the compact tau; the apply only reads them. Q is the full m x m
- * orthogonal factor (Q^T A = [R; 0]). C is m x nrhs, column-major, of the handle's dtype, with
+ * device: R, the V tiles and the compact tau; the apply only reads them. Of dA, prepare and apply_q
+ * use as values only the elements strictly below the diagonal, in tile columns k < kmax (the V of the
+ * GEQRT and TSQRT tiles): R on and above the diagonal of a diagonal tile is loaded with its column
+ * and replaced by the unit-lower trapezoid's 0 / 1 through a select, and the tiles above the block
+ * diagonal are never read — whatever R holds, inf and NaN included, cannot reach C (the mirror image
+ * of tqr_trsm_r's rule below). Q is the full m x m orthogonal factor (Q^T A = [R; 0]). C is m x nrhs, column-major, of the handle's dtype, with
  * leading dimension lddc >= m; nrhs >= 1 need not be a multiple of anything. Rows >= m and columns
  * >= nrhs of C's allocation are not touched. ldda and lddc obey the library's leading-dimension
  * bound (above).

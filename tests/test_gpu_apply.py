@@ -17,15 +17,18 @@ import ctypes
 import numpy as np
 import pytest
 
+from inputs import numpy_q, oracle_qt, reflectors  # noqa: F401 (shared with the other apply / solve tests)
+
 pytestmark = pytest.mark.gpu
 
 P = ctypes.c_void_p
 # the smallest shapes at which each mechanism exists (m, n, b): one group per tile; two groups (the GE
 # group's skipped zero k-steps); 4 and 8 groups (the production tile); wide (kmax = p); tall (a TS
-# chain of 3 under one panel). All have p >= 2, kmax >= 2.
+# chain of 3 under one panel); a single tile row (p = 1: no TSMQR at all), wide and square; a tall chain
+# (9 TSMQR tiles under each UNMQR).
 SHAPES = [(48, 32, 16), (96, 64, 32), (192, 128, 64), (384, 256, 128), (768, 512, 256), (256, 384, 128),
-          (1024, 256, 256)]
-SHAPES32 = [(192, 128, 64), (768, 512, 256)]
+          (1024, 256, 256), (64, 128, 64), (256, 256, 256), (1280, 256, 128)]
+SHAPES32 = [(48, 32, 16), (96, 64, 32), (192, 128, 64), (384, 256, 128), (768, 512, 256), (256, 384, 128)]
 NRHS = [1, 17, 64, 80]  # one lane, a ragged wave, one full workgroup, two workgroups (the second ragged)
 NMAX = max(NRHS)
 CASES = [(s, np.float64) for s in SHAPES] + [(s, np.float32) for s in SHAPES32]
@@ -54,66 +57,6 @@ def rhs(oracle, shape, dt, seed=23):
         C.setflags(write=False)
         _cache[key] = C
     return _cache[key]
-
-
-def oracle_qt(oracle, F, T, C, b):
-    """Q^T C by the oracle's tile kernels: [F | C] in one array of leading dimension m, C padded to
-    whole b-column blocks, the factorisation's order block column by block column."""
-    n, m = F.shape
-    nrhs = C.shape[0]
-    p, q = m // b, n // b
-    kmax = min(p, q)
-    nb = (nrhs + b - 1) // b
-    W = np.zeros((n + nb * b, m), dtype=F.dtype)
-    W[:n] = F
-    W[n:n + nrhs] = C
-    Tc = np.ascontiguousarray(T)
-    es, wb, tb = W.itemsize, W.ctypes.data, Tc.ctypes.data
-    sfx = oracle.sfx(F.dtype)
-    unmqr, tsmqr = getattr(oracle.L, f"oracle_unmqr_{sfx}"), getattr(oracle.L, f"oracle_tsmqr_{sfx}")
-
-    def tile(r, c):
-        return P(wb + (c * b * m + r * b) * es)
-
-    def taus(r, k):
-        return P(tb + (k * b * m + r * b) * es)
-
-    for j in range(q, q + nb):
-        for k in range(kmax):
-            unmqr(tile(k, j), tile(k, k), taus(k, k), b, b, m)
-            for l in range(k + 1, p):
-                tsmqr(tile(l, k), tile(k, j), tile(l, j), taus(l, k), b, b, m)
-    return W[n:n + nrhs].copy()
-
-
-def reflectors(F, T, b):
-    """The factorisation's reflectors in application order: (rows, v, tau) with v over `rows`."""
-    n, m = F.shape
-    p, q = m // b, n // b
-    out = []
-    for k in range(min(p, q)):
-        for c in range(b):
-            d = k * b + c
-            rows = np.arange(d, (k + 1) * b)
-            v = F[d, rows].copy()
-            v[0] = 1.0
-            out.append((rows, v, T[k * b, d]))
-        for l in range(k + 1, p):
-            for c in range(b):
-                d = k * b + c
-                rows = np.concatenate(([d], np.arange(l * b, (l + 1) * b)))
-                v = np.concatenate(([1.0], F[d, l * b:(l + 1) * b])).astype(F.dtype)
-                out.append((rows, v, T[k * b, l * b + c]))
-    return out
-
-
-def numpy_q(F, T, C, b):
-    """Q C: the reflectors I - tau v v^T one by one in reverse, in the arrays' own precision."""
-    C = C.copy()
-    for rows, v, tau in reversed(reflectors(F, T, b)):
-        w = C[:, rows] @ v
-        C[:, rows] -= np.outer(tau * w, v)
-    return C
 
 
 def reference(oracle, shape, dt, trans):

@@ -5,7 +5,8 @@ References (never the GPU). tqr_trsm_r: F is the oracle's factorisation of a RAN
 n rows of another; the fp64 upper triangle of F is solved by numpy.linalg.solve, and the residual
 op(R) x - y is formed in numpy.longdouble. tqr_lstsq: numpy.linalg.lstsq on the original matrix (the
 factorisation itself runs on the GPU, TiledQR). All matrices are well conditioned (asserted), so a
-wrong answer cannot hide behind conditioning.
+wrong answer cannot hide behind conditioning. Conditioned and structured inputs, and leading dimensions
+at the library's bound: tests/test_gpu_solve_inputs.py.
 
 Tolerances (derived, not tuned; u = 2^-53 for fp64, 2^-24 for fp32 storage):
   backward, componentwise:  |op(R) x - y| <= n u (|op(R)| |x| + |y|) element by element — the
@@ -27,7 +28,7 @@ P = ctypes.c_void_p
 # (m, n, b): one 32-row group per tile (b = 16: one 16-row group), 2, 4 and 8 groups, two tile rows of R
 # in each, and a single tile
 SHAPES = [(48, 32, 16), (96, 64, 32), (192, 128, 64), (384, 256, 128), (768, 512, 256), (1024, 256, 256)]
-SHAPES32 = [(192, 128, 64), (768, 512, 256)]
+SHAPES32 = [(48, 32, 16), (96, 64, 32), (192, 128, 64), (384, 256, 128), (768, 512, 256)]
 NRHS = [1, 17, 64, 80]  # one lane, a ragged wave, one full workgroup, two workgroups (the second ragged)
 NMAX = max(NRHS)
 CASES = [(s, np.float64) for s in SHAPES] + [(s, np.float32) for s in SHAPES32]
@@ -81,8 +82,9 @@ def gpu_solve(tqr, F, Y, b, trans, stream=None):
     return dX.cpu().numpy()
 
 
-def check_solution(got, R, Y, Xref, trans, dt, what=""):
-    """got (nrhs, n) against the two accuracy rules of the module docstring."""
+def check_backward(got, R, Y, trans, dt, what=""):
+    """got (nrhs, n): finite, and the componentwise backward rule of the module docstring (it holds at
+    any condition number). Returns the largest ratio in units of u."""
     n = R.shape[0]
     u = unit(dt)
     ld = np.longdouble
@@ -92,11 +94,18 @@ def check_solution(got, R, Y, Xref, trans, dt, what=""):
     bound = np.abs(op) @ np.abs(x) + np.abs(y)
     nz = bound > 0  # (an all-zero row of the bound has a zero residual: asserted below with the rest)
     ratio = float((resid[nz] / (u * bound[nz])).max())  # in units of u; the rule is <= n
-    err = float(np.abs(got.T.astype(np.float64) - Xref).max())
-    scale = max(1.0, float(np.abs(Xref).max()))
-    print(f"{what} backward {ratio:.2f} u (allowed {n} u), forward max|x - x_ref| = {err:.3e} (max|x_ref| {scale:.3e})")
+    print(f"{what} backward {ratio:.2f} u (allowed {n} u), max|x| {float(np.abs(got).max()):.3e}")
     assert np.all(np.isfinite(got))
     assert np.all(resid <= n * u * bound)
+    return ratio
+
+
+def check_solution(got, R, Y, Xref, trans, dt, what=""):
+    """got (nrhs, n) against the two accuracy rules of the module docstring."""
+    check_backward(got, R, Y, trans, dt, what)
+    err = float(np.abs(got.T.astype(np.float64) - Xref).max())
+    scale = max(1.0, float(np.abs(Xref).max()))
+    print(f"{what} forward max|x - x_ref| = {err:.3e} (max|x_ref| {scale:.3e})")
     assert err <= (1e-11 if np.dtype(dt) == np.float64 else 1e-4) * scale
 
 
@@ -109,6 +118,25 @@ def test_trsm_r_accuracy(tqr, oracle, shape, dt, trans, nrhs):
     got = gpu_solve(tqr, F, Y[:nrhs], shape[2], trans)
     assert got.shape == (nrhs, shape[1]) and got.dtype == np.dtype(dt)
     check_solution(got, R, Y[:nrhs], Xref[:, :nrhs], trans, dt)
+
+
+@pytest.mark.parametrize("nrhs", [17, 80])
+@pytest.mark.parametrize("trans", TRANS, ids=TIDS)
+def test_trsm_r_square_single_tile(tqr, oracle, trans, nrhs):
+    """m = n = b = 256: R is the one tile of a factorisation with a single tile row. A square RANDZO
+    matrix is not as well conditioned as the tall ones of problem() (cond(R) about 2e3, asserted below
+    1e4 as in test_lstsq_square_residual_is_zero), which both rules of check_solution carry as they
+    stand: cond u is about 2e-13 of the forward rule's 1e-11."""
+    m = n = b = 256
+    A = oracle.randzo(m, n, np.float64, seed=11 + b)
+    F, _ = oracle.factor(A, b)
+    R = np.triu(F.T)
+    cond = float(np.linalg.cond(R))
+    assert cond < 1e4, cond
+    Y = np.ascontiguousarray(oracle.randzo(m, nrhs, np.float64, seed=23))
+    Xref = np.linalg.solve(R.T if trans else R, Y.T)
+    got = gpu_solve(tqr, F, Y, b, trans)
+    check_solution(got, R, Y, Xref, trans, np.float64, f"cond {cond:.0f}:")
 
 
 @pytest.mark.parametrize("trans", TRANS, ids=TIDS)
@@ -181,8 +209,9 @@ def test_non_default_stream_same_bits(tqr, oracle, trans):
 
 
 # ---- tqr_lstsq --------------------------------------------------------------------------------
+# (the last: a tall chain, 10 tile rows under each panel)
 LSQ = [((768, 256, 128), np.float64), ((1024, 256, 256), np.float64), ((768, 512, 256), np.float64),
-       ((192, 128, 64), np.float32)]
+       ((192, 128, 64), np.float32), ((1280, 256, 128), np.float64)]
 LSQ_IDS = [f"{m}x{n}b{b}-{'f64' if dt == np.float64 else 'f32'}" for (m, n, b), dt in LSQ]
 
 

@@ -332,6 +332,55 @@ def test_form_qt(tqr, oracle, m, n, b):
     check_apply(Qt.cpu().numpy(), ref, ref, "form_qt against the apply to an identity:")
 
 
+def test_form_qt_rowgraded(tqr):
+    """Q^T of a row-graded matrix (cond about 1e8, tests/inputs.py) is as orthogonal as that of a
+    well-conditioned one: max|Q^T Q - I| at test_form_qt's bound, and Q^T A = [R; 0] relative to max|A|."""
+    import torch
+    import inputs
+    m, n, b = shape = (256, 128, 64)
+    A = inputs.matrix("rowgraded", shape)
+    Qt, F, tau = tqr.form_qt(torch.from_numpy(A.copy()).cuda(), b)
+    torch.cuda.synchronize()
+    QT = Qt.cpu().numpy().T
+    got = QT @ A.T
+    R = np.triu(F.cpu().numpy().T)
+    up = np.arange(m)[:, None] <= np.arange(n)[None, :]
+    e_up, e_lo = float(np.abs(got - R)[up].max()), float(np.abs(got)[~up].max())
+    e_orth = float(np.abs(QT @ QT.T - np.eye(m)).max())
+    print(f"max|triu(Q^T A) - R| = {e_up:.3e}, below the diagonal {e_lo:.3e}, max|Q^T Q - I| = {e_orth:.3e}")
+    assert np.isfinite(QT).all()
+    assert e_orth <= 1e-11
+    assert e_up <= 1e-11 * max(1.0, float(np.abs(R).max()))
+    assert e_lo <= 1e-11 * float(np.abs(A).max())
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.float32], ids=dn)
+@pytest.mark.parametrize("m,n,b,nrhs", [(384, 256, 64, 17), (1024, 512, 256, 257)])
+def test_lstsq_fused_poisoned_padding(tqr, oracle, m, n, b, nrhs, dt):
+    """NaN in the padding columns nrhs .. r*b-1 on entry: X, the rows n .. m-1 of Q^T B, the residual
+    norms, the factorisation of A and tau are the bits of the run with zero padding (include/tqr.h:
+    "what they hold on entry influences nothing else"), and the NaN stays in the padding."""
+    import torch
+    A, B, _ = lsq_problem(oracle, m, n, b, dt)
+    r = -(-nrhs // b)
+    assert nrhs < r * b
+    outs = []
+    for pad in (0.0, float("nan")):
+        AB = torch.full((n + r * b, m), pad, dtype=tdt(dt), device="cuda")
+        AB[:n] = torch.from_numpy(A.copy()).cuda()
+        AB[n:n + nrhs] = torch.from_numpy(B[:nrhs].copy()).cuda()
+        plan = tqr.TiledQR(m, n + r * b, b, AB.dtype, steps=n // b)
+        tau = torch.zeros((n // b, m), dtype=AB.dtype, device="cuda")
+        res = torch.full((nrhs,), -1.0, dtype=AB.dtype, device="cuda")
+        plan.lstsq_fused(AB, tau, nrhs, res=res)
+        plan.status()
+        outs.append((AB.cpu(), tau.cpu(), res.cpu()))
+    (AB0, tau0, res0), (AB1, tau1, res1) = outs
+    assert bool(torch.isfinite(AB0).all()) and bool(torch.isfinite(res0).all())
+    assert torch.equal(AB1[:n + nrhs], AB0[:n + nrhs]) and torch.equal(tau1, tau0) and torch.equal(res1, res0)
+    assert bool(torch.isnan(AB1[n + nrhs:]).all())
+
+
 # ---- (g) argument errors on live objects --------------------------------------------------------
 def test_einval_on_live_plans(tqr):
     import torch
