@@ -21,7 +21,7 @@
 #include <cstring>
 
 #include "solve.hpp"
-#include "tiles.hpp"
+#include "solve_dev.hpp"
 #include "tqr.h"
 
 namespace tqr {
@@ -33,142 +33,8 @@ struct SolveArgs {
   int nt, nrhs;   // nt = n / b tile rows
 };
 
-// ---------------------------------------------------------------------------------------
-// Operand image of 32 target rows (group g of a tile row; b < 32: the tile's b rows) in the LDS V
-// layout of tiles.hpp (b x VP doubles, column permutation pc), negated, so that accum_z forms
-//   Z = H + V^T X_k = H - (the group's rows of op(R) tile) X_k :
-//   TR  (X <- R^{-1} X):  V[kk][c] = -tile(g IB + c, kk)   — the group's 32 rows, transposed;
-//   !TR (X <- R^{-T} X):  V[kk][c] = -tile(kk, g IB + c)   — the group's 32 columns as stored.
-// The tile is read in IB x IB chunks kc0 <= kc < kc1 of the k index through a buffer resource
-// based at the chunk (32-bit offsets over <= 32 columns: the leading-dimension bound), 32
-// consecutive lanes on 32 consecutive elements of a column. DIAG (tile (k,k)): an element below
-// the diagonal — the GEQRT V, whatever it holds — becomes 0 by a select.
-// ---------------------------------------------------------------------------------------
-template <int B, typename S, bool TR, bool DIAG>
-__device__ __forceinline__ void stage_r(double* Vs, const S* __restrict__ rt, size_t ldm, int g, int kc0, int kc1) {
-  using G = Geo<B>;
-  constexpr int IB = G::IB, PER = IB * IB / NT, SB = G::NG < 4 ? G::NG : 4;
-  static_assert(IB * IB % NT == 0, "whole passes of the workgroup over a chunk");
-  // SB chunks per batch: all of a batch's loads are issued before its first LDS store (left to the
-  // compiler, every load is waited for and stored before the next is issued — one memory round
-  // trip per element). A batch that reaches past kc1 repeats the last chunk (the same values to
-  // the same places) instead of branching around loads.
-  for (int k0 = kc0; k0 < kc1; k0 += SB) {
-    double v[SB][PER];
-#pragma unroll
-    for (int u = 0; u < SB; ++u) {
-      const int kc = k0 + u < kc1 ? k0 + u : kc1 - 1;
-      const S* base = TR ? rt + (size_t)kc * IB * ldm + (size_t)g * IB : rt + (size_t)g * IB * ldm + (size_t)kc * IB;
-      const __amdgpu_buffer_rsrc_t rs = uniform_rsrc(base);
-#pragma unroll
-      for (int it = 0; it < PER; ++it) {
-        const int idx = it * NT + threadIdx.x;
-        const int ar = idx % IB, ac = idx / IB;  // (row, column) inside the chunk as stored
-        const unsigned off = (unsigned)(((size_t)ac * ldm + ar) * sizeof(S));
-        if constexpr (sizeof(S) == 8) {
-          const auto w = __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0);
-          v[u][it] = dbl_of(w[0], w[1]);
-        } else {
-          v[u][it] = (double)__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
-        }
-      }
-    }
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int u = 0; u < SB; ++u) {
-      const int kc = k0 + u < kc1 ? k0 + u : kc1 - 1;
-#pragma unroll
-      for (int it = 0; it < PER; ++it) {
-        const int idx = it * NT + threadIdx.x;
-        const int ar = idx % IB, ac = idx / IB;
-        const int c = TR ? ar : ac, kk = kc * IB + (TR ? ac : ar);
-        double e = v[u][it];
-        if (DIAG) {
-          const int row = TR ? g * IB + c : kk, colm = TR ? kk : g * IB + c;  // element of the tile
-          e = row > colm ? 0.0 : e;
-        }
-        Vs[kk * G::VP + G::pc(c)] = -e;
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// The IB x IB diagonal block of a group by substitution, on Z (the group's IB rows of the strip:
-// Z[r] at lane row x = row 4r + x, every column on 4 lanes 16 apart). Vd = the image rows of the
-// block's own k range: Vd[j][pc(i)] = -D(i, j) (TR) / -D(j, i) (!TR) — the lane of row i = 4r + x
-// finds its NRI coefficients of step j contiguous at Vd[j * VP + x * NRI + r].
-// Step j (descending for the upper triangle, ascending for its transpose): the lane holding row j
-// divides by the diagonal entry itself, the quotient goes to the column's 4 lanes (ds_bpermute),
-// and the rows still to be solved take z_i <- z_i - D_ij x_j. Rows already solved, and the
-// coefficients on the other side of the diagonal, are excluded by selects (not by a zero factor:
-// an inf or NaN there must not leak).
-// ---------------------------------------------------------------------------------------
-template <int B, bool TRANS>
-__device__ __forceinline__ void subst(const double* __restrict__ Vd, double (&Z)[Geo<B>::NRI]) {
-  using G = Geo<B>;
-  constexpr int IB = G::IB, NRI = G::NRI, VP = G::VP;
-  const int lane = threadIdx.x & 63, x = lane >> 4;
-  const unsigned vb = lds_base(Vd + x * NRI);
-  // the lane's coefficients of step jj: the registers with a row still to be solved (upper triangle:
-  // r <= j / 4, its transpose: r >= j / 4), in 16-B reads
-  auto ldc = [&](double (&c)[NRI], int jj) {
-    const int j = TRANS ? jj : IB - 1 - jj, jr = j >> 2;
-    const int r0 = TRANS ? jr : 0, r1 = TRANS ? NRI - 1 : jr;
-#pragma unroll
-    for (int h = 0; h < NRI / 2; ++h)
-      if (2 * h + 1 >= r0 && 2 * h <= r1) {
-        const d2v_t t = lds_rd2(vb + (unsigned)((j * VP + 2 * h) * sizeof(double)));
-        c[2 * h] = t.x;
-        c[2 * h + 1] = t.y;
-      }
-  };
-  double cf[NRI], cn[NRI];
-  ldc(cf, 0);
-#pragma unroll
-  for (int jj = 0; jj < IB; ++jj) {
-    // one step per scheduling region, the next step's coefficients read ahead (left free, the
-    // scheduler hoists the reads of all IB steps: the chain is serial, the reads are not)
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" ::: "memory");
-    const int j = TRANS ? jj : IB - 1 - jj, jr = j >> 2, jx = j & 3;
-    const int r0 = TRANS ? jr : 0, r1 = TRANS ? NRI - 1 : jr;
-    if (jj + 1 < IB) ldc(cn, jj + 1);
-    double q = Z[jr] / -cf[jr];  // (lane row jx: z_j / D_jj; the image is negated)
-    q = __shfl(q, 16 * jx + (lane & 15));
-#pragma unroll
-    for (int r = r0; r <= r1; ++r) {
-      if (r == jr) Z[r] = x == jx ? q : ((TRANS ? x > jx : x < jx) ? fma(cf[r], q, Z[r]) : Z[r]);
-      else Z[r] = fma(cf[r], q, Z[r]);
-      // (the update belongs to this step: left to the compiler, the forward direction keeps every
-      // step's quotient and coefficients in registers and updates a row only when its turn comes)
-      asm volatile("" : "+v"(Z[r]));
-    }
-#pragma unroll
-    for (int r = 0; r < NRI; ++r) cf[r] = cn[r];
-  }
-}
-
-// Target rows of a tile row (32-bit offsets through the wave's resource, as apply.hip): a lane whose
-// column is >= nrhs (`on` false) loads zeros and stores nothing.
-template <int B, typename S>
-__device__ __forceinline__ void load_h(double (&H)[Geo<B>::NRI], __amdgpu_buffer_rsrc_t rs, unsigned off, bool on) {
-  if (on) {
-    load_head_buf<B, S, 0>(H, rs, off);
-  } else {
-#pragma unroll
-    for (int r = 0; r < Geo<B>::NRI; ++r) H[r] = 0.0;
-  }
-}
-template <int B, typename S>
-__device__ __forceinline__ void load_x(double (&X)[Geo<B>::NKS], __amdgpu_buffer_rsrc_t rs, unsigned off, bool on) {
-  if (on) {
-    load_strip_buf<B, S, 0>(X, rs, off, 0);
-  } else {
-#pragma unroll
-    for (int ks = 0; ks < Geo<B>::NKS; ++ks) X[ks] = 0.0;
-  }
-}
+// (the operand images stage_r, the substitution subst and the strip loads load_h / load_x, which
+// solve_pipe.hip's kernel shares: solve_dev.hpp)
 
 // ---------------------------------------------------------------------------------------
 // solve: X <- R^{-T} X (TRANS) or X <- R^{-1} X. Workgroup blockIdx.x owns columns 64 blockIdx.x ..
@@ -291,12 +157,7 @@ static sfn solve_kernel(int dtype, int trans) {
   if (dtype == TQR_F64) return trans == TQR_TRANS ? k_trsm_r<B, double, true> : k_trsm_r<B, double, false>;
   return trans == TQR_TRANS ? k_trsm_r<B, float, true> : k_trsm_r<B, float, false>;
 }
-// dynamic LDS (bytes): one operand image, b x (IB + 2) doubles (Geo<b>::VSZ)
-static size_t lds_solve(int b) { return (size_t)b * ((b < 32 ? b : 32) + 2) * sizeof(double); }
-static_assert(Geo<256>::VSZ * sizeof(double) == 69632 && Geo<16>::VSZ == 16 * 18, "host lds_solve mirrors Geo::VSZ");
-static bool solve_valid_b(int b) { return b == 16 || b == 32 || b == 64 || b == 128 || b == 256; }
-// the library's leading-dimension bound (include/tqr.h): 32 * ld * sizeof(element) < 2^31
-static bool solve_valid_ld(long ld, size_t es) { return ld > 0 && (size_t)32 * (size_t)ld * es <= 0x7fffffffull; }
+// (lds_solve, solve_valid_b, solve_valid_ld: solve_dev.hpp)
 
 #define HIPCHK(x)                                                                         \
   do {                                                                                    \

@@ -111,6 +111,20 @@ def lib():
     L.tqr_lstsq.restype = _I
     L.tqr_lstsq_fused.argtypes = [_P, _P, _I, _P, _I, _P, _P]
     L.tqr_lstsq_fused.restype = _I
+    L.tqr_solve_create.argtypes = [ctypes.POINTER(_P), _I, _I, _I, _I]
+    L.tqr_solve_create.restype = _I
+    L.tqr_solve_workspace_bytes.argtypes = [_P]
+    L.tqr_solve_workspace_bytes.restype = ctypes.c_size_t
+    L.tqr_solve_trsm_r.argtypes = [_P, _I, _P, _I, _P, _I, _I, _P]
+    L.tqr_solve_trsm_r.restype = _I
+    L.tqr_solve_status.argtypes = [_P, _P]
+    L.tqr_solve_status.restype = _I
+    L.tqr_solve_destroy.argtypes = [_P]
+    L.tqr_solve_destroy.restype = None
+    L.tqr_solve_ticket.argtypes = [_I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]
+    L.tqr_solve_ticket.restype = _I
+    L.tqr_lstsq_fused_solve.argtypes = [_P, _P, _P, _I, _P, _I, _P, _P]
+    L.tqr_lstsq_fused_solve.restype = _I
     _lib = L
     return L
 
@@ -198,12 +212,19 @@ class TiledQR:
         """Synchronise `stream` and raise if the engine reported an error (tqr_plan_status)."""
         check(lib().tqr_plan_status(self.h, _P(stream or 0)), "tqr_plan_status")
 
-    def lstsq_fused(self, AB, tau, nrhs, res=None, ldda=None, stream=None):
+    def lstsq_fused(self, AB, tau, nrhs, res=None, ldda=None, stream=None, solve=None):
         """tqr_lstsq_fused on a capped plan over [A | B] (steps = A's tile columns): AB (n, ldda) in
-        place, tau (steps, m); `res` (optional) receives the nrhs residual norms. Stream-ordered."""
+        place, tau (steps, m); `res` (optional) receives the nrhs residual norms. Stream-ordered.
+        solve: a Solve handle for (steps * b, b, dtype) — the triangular solve then runs pipelined over
+        workgroups (tqr_lstsq_fused_solve), with the same bits."""
         ldda = ldda or self.m
-        check(lib().tqr_lstsq_fused(self.h, _ptr(AB), ldda, _ptr(tau), nrhs, None if res is None else _ptr(res),
-                                    _stream_handle(stream)), "tqr_lstsq_fused")
+        pres = None if res is None else _ptr(res)
+        if solve is None:
+            check(lib().tqr_lstsq_fused(self.h, _ptr(AB), ldda, _ptr(tau), nrhs, pres, _stream_handle(stream)),
+                  "tqr_lstsq_fused")
+        else:
+            check(lib().tqr_lstsq_fused_solve(self.h, solve.h, _ptr(AB), ldda, _ptr(tau), nrhs, pres,
+                                              _stream_handle(stream)), "tqr_lstsq_fused_solve")
 
     def set_profile(self, on=True):
         check(lib().tqr_plan_set_profile(self.h, int(on)))
@@ -499,17 +520,70 @@ class ApplyQ:
             pass
 
 
-def trsm_r(F, X, b, trans=False, n=None, nrhs=None, ldda=None, lddx=None, stream=None):
+class Solve:
+    """The triangular solve with R pipelined over workgroups (tqr_solve, include/tqr.h "pipelined
+    solve"): the bits of trsm_r, on n / b CUs per 64 right-hand sides instead of one — the call for a
+    narrow X. Create once per (n, b, dtype) and largest nrhs; calls on one handle are serialised on
+    the GPU and need no host synchronisation in between."""
+
+    def __init__(self, n, b, dtype, nrhs_max):
+        self.n, self.b, self.nrhs_max = n, b, nrhs_max
+        self.dtype = dtype if isinstance(dtype, int) else _dtype_code(dtype)
+        self.h = None
+        h = _P()
+        check(lib().tqr_solve_create(ctypes.byref(h), n, b, self.dtype, nrhs_max), "tqr_solve_create")
+        self.h = h
+
+    def workspace_bytes(self):
+        return int(lib().tqr_solve_workspace_bytes(self.h))
+
+    def trsm_r(self, F, X, trans=False, nrhs=None, ldda=None, lddx=None, stream=None):
+        """X (>= nrhs, lddx) <- R^{-1} X (or R^{-T} X with trans) in place, R the upper triangle of the
+        leading n x n block of F (>= n, ldda); as tqr.trsm_r. Stream-ordered."""
+        if X.dtype != F.dtype or _dtype_code(F.dtype) != self.dtype:
+            raise TQRError("Solve.trsm_r: F and X must be of the handle's dtype")
+        nrhs = X.shape[0] if nrhs is None else nrhs
+        ldda = ldda or F.shape[-1]
+        lddx = lddx or X.shape[-1]
+        check(lib().tqr_solve_trsm_r(self.h, 1 if trans else 0, _ptr(F), ldda, _ptr(X), nrhs, lddx,
+                                     _stream_handle(stream)), "tqr_solve_trsm_r")
+
+    def status(self, stream=None):
+        """Synchronise `stream` and the handle's last call; raise if a wait timed out (tqr_solve_status)."""
+        check(lib().tqr_solve_status(self.h, _stream_handle(stream)), "tqr_solve_status")
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().tqr_solve_destroy(self.h)
+        except Exception:
+            pass
+
+
+def solve_ticket(T, nstrips, trans, ticket):
+    """Host-only: (strip, row) of a ticket of the pipelined solve (tqr_solve_ticket)."""
+    st, row = _I(), _I()
+    check(lib().tqr_solve_ticket(T, nstrips, 1 if trans else 0, ticket, ctypes.byref(st), ctypes.byref(row)),
+          "tqr_solve_ticket")
+    return st.value, row.value
+
+
+def trsm_r(F, X, b, trans=False, n=None, nrhs=None, ldda=None, lddx=None, stream=None, solve=None):
     """X <- R^{-1} X (or R^{-T} X with trans) in place, R the upper triangle of the leading n x n block
     of the factorised F (tqr_trsm_r, include/tqr.h "solve"). F (>= n, ldda) and X (>= nrhs, lddx) are
     device tensors of one dtype; n defaults to F's column count, nrhs, ldda and lddx to the tensors'
-    shapes. No handle and no workspace. Stream-ordered."""
+    shapes. No handle and no workspace. Stream-ordered. solve: a Solve handle made for (n, b, dtype) —
+    the same bits from the pipelined kernel (Solve.trsm_r), the faster call for a narrow X."""
     if X.dtype != F.dtype:
         raise TQRError("trsm_r: F and X must be of one dtype")
     n = F.shape[0] if n is None else n
     nrhs = X.shape[0] if nrhs is None else nrhs
     ldda = ldda or F.shape[-1]
     lddx = lddx or X.shape[-1]
+    if solve is not None:
+        if solve.n != n or solve.b != b:
+            raise TQRError(f"trsm_r: the Solve handle is for n = {solve.n}, b = {solve.b}, not {n}, {b}")
+        return solve.trsm_r(F, X, trans=trans, nrhs=nrhs, ldda=ldda, lddx=lddx, stream=stream)
     check(lib().tqr_trsm_r(_dtype_code(F.dtype), 1 if trans else 0, n, b, _ptr(F), ldda, _ptr(X), nrhs, lddx,
                            _stream_handle(stream)), "tqr_trsm_r")
 
@@ -538,13 +612,14 @@ def lstsq(F, tau, B, b):
     return X, res
 
 
-def lstsq_fused(A, B, b):
+def lstsq_fused(A, B, b, solve=None):
     """Least squares min |A x - b| for every column of B with the factorisation itself, in one
     pipelined launch (tqr_lstsq_fused, include/tqr.h): A (n, m) and B (nrhs, m) are device tensors of
     one dtype, m >= n (row j = column j, as everywhere in this module). Builds [A | B padded with zero
     columns to whole tiles], runs a capped plan over it, and returns (X (nrhs, n), res (nrhs,), F, tau):
     F (n, m) and tau (n / b, m) are an ordinary factorisation of A — ApplyQ(m, n).prepare(F, tau) and
-    trsm_r(F, ...) work on them. A and B are not modified."""
+    trsm_r(F, ...) work on them. A and B are not modified. solve: a Solve handle for (n, b, dtype) with
+    nrhs_max >= nrhs — the triangular solve then runs pipelined over workgroups, with the same bits."""
     import torch
     n, m = A.shape
     if m < n:
@@ -560,8 +635,10 @@ def lstsq_fused(A, B, b):
     tau = torch.zeros((n // b, m), dtype=A.dtype, device=A.device)
     res = torch.empty((nrhs,), dtype=A.dtype, device=A.device)
     cs = torch.cuda.current_stream()
-    plan.lstsq_fused(AB, tau, nrhs, res=res, stream=cs)
+    plan.lstsq_fused(AB, tau, nrhs, res=res, stream=cs, solve=solve)
     plan.status(cs.cuda_stream)
+    if solve is not None:
+        solve.status(cs)
     return AB[n:n + nrhs, :n], res, AB[:n], tau
 
 

@@ -243,6 +243,64 @@ int tqr_lstsq(tqr_apply* ap, int trans, const void* dA, int ldda, void* dB, int 
  * or nrhs > r*b; a bad ldda. Status of the launch: tqr_plan_status, as after tqr_plan_execute. */
 int tqr_lstsq_fused(tqr_plan* plan, void* dAB, int ldda, void* dtau_compact, int nrhs, void* dres, void* stream);
 
+/* ---- pipelined solve: tqr_trsm_r spread over workgroups, for narrow right-hand sides ----------
+ * tqr_solve_trsm_r computes what tqr_trsm_r computes, bit for bit, and its semantics are
+ * tqr_trsm_r's word for word: X <- R^{-1} X (TQR_NOTRANS) or X <- R^{-T} X (TQR_TRANS) in place, R
+ * the upper triangle of the leading n x n block of dA; only elements (i, j) with i <= j < n are read
+ * as values, everything below the diagonal of the diagonal tiles is masked by a select; dA is not
+ * written; rows >= n and columns >= nrhs of X's allocation are not touched; a zero diagonal entry,
+ * inf and NaN propagate exactly as there (the same operations in the same order); fp32 storage
+ * computes in fp64 and rounds a tile row to float whenever it is stored.
+ * Method: one workgroup per (64-column strip of X, tile row of R) instead of one per strip. The
+ * workgroup of tile row i waits for each solved X_k it depends on (k > i, descending, for R; k < i,
+ * ascending, for R^T), subtracts op(R)_ik X_k from its own rows, and finally solves against tile
+ * (i,i) and publishes X_i through a flag in the handle's workspace — so a narrow X occupies n / b
+ * CUs instead of one, and the serial chain is one tile update plus one diagonal tile per tile row.
+ * With many strips (nrhs of the order of n) tqr_trsm_r already fills the device and is the faster
+ * call (DESIGN.md §15 has the crossover); nothing here replaces it.
+ * Work items are handed out by an atomic ticket in dependency order, so a workgroup only ever waits
+ * for workgroups that are already running, however few fit on the device. Every wait is bounded
+ * (5 s): on expiry the kernel sets the handle's error word and all its workgroups leave — it
+ * cannot hang. tqr_solve_status synchronises `stream` and the handle's last call and returns
+ * TQR_OK, or TQR_EHIP once after a wait timed out (X is then undefined; the handle stays usable).
+ *
+ * tqr_solve_create: a handle for n x n triangles of tile size b (b in {16, 32, 64, 128, 256} dividing
+ * n) and `dtype`, for up to nrhs_max >= 1 right-hand sides. It owns tqr_solve_workspace_bytes of
+ * device memory: the ticket counter, the error word and one flag per (strip, tile row) — 4 bytes
+ * each, ceil(nrhs_max / 64) * (n / b) flags. Calls allocate nothing.
+ * A handle's calls are serialised like a plan's executes: concurrent host threads are mutually
+ * excluded while they enqueue, and each call's stream first waits for the handle's previous call
+ * (whatever its stream), so two calls of one handle never overlap on the GPU; use one handle per
+ * concurrent solve. Consecutive calls need no host synchronisation: flags carry a per-call epoch
+ * and the ticket counter is re-armed in stream order.
+ * Every argument error returns TQR_EINVAL before any device call: create with a bad dtype, a b
+ * outside the list or not dividing n, n <= 0, nrhs_max < 1, or a shape whose grid would pass 2^31
+ * workgroups; tqr_solve_trsm_r with a NULL handle or pointer, a bad trans, nrhs < 1 or > nrhs_max,
+ * ldda or lddx below n or beyond the library's leading-dimension bound. A missing or non-gfx950
+ * device is reported after that validation: tqr_solve_create then still returns a handle (without
+ * device memory), and every tqr_solve_trsm_r on it returns TQR_ENODEV.
+ *
+ * tqr_solve_ticket (host only, no GPU): the work item (*strip, *row) of ticket `ticket` on T tile
+ * rows and nstrips strips — the function the kernel itself evaluates. Tickets 0 .. T*nstrips-1 map
+ * one to one onto the items, and every item a row waits for (rows above it for TQR_TRANS, below it
+ * for TQR_NOTRANS, same strip) has a smaller ticket. Anything out of range returns TQR_EINVAL.
+ *
+ * tqr_lstsq_fused_solve: tqr_lstsq_fused with tqr_solve_trsm_r in place of tqr_trsm_r; same
+ * arguments, same results bit for bit. sv must have been created for (steps * b, b, the plan's dtype)
+ * with nrhs_max >= nrhs, else TQR_EINVAL (with tqr_lstsq_fused's own argument errors, before any
+ * device call). Launch status: tqr_plan_status for the factorisation, tqr_solve_status for the solve.
+ * tqr_lstsq has no such variant: its apply strip, not the solve, dominates a narrow call. */
+typedef struct tqr_solve tqr_solve;
+int tqr_solve_create(tqr_solve** sv, int n, int b, int dtype, int nrhs_max);
+size_t tqr_solve_workspace_bytes(const tqr_solve* sv);
+int tqr_solve_trsm_r(tqr_solve* sv, int trans, const void* dA, int ldda, void* dX, int nrhs, int lddx,
+                     void* stream);
+int tqr_solve_status(tqr_solve* sv, void* stream);
+void tqr_solve_destroy(tqr_solve* sv);
+int tqr_solve_ticket(int T, int nstrips, int trans, int ticket, int* strip, int* row);
+int tqr_lstsq_fused_solve(tqr_plan* plan, tqr_solve* sv, void* dAB, int ldda, void* dtau_compact, int nrhs,
+                          void* dres, void* stream);
+
 /* ---- multi-GPU: tile-column partition, one process per GPU ---------------------------------
  * Rank r owns the tile columns j with tqr_dist_owner(j) == r — snake order over the ranks
  * (0..W-1, W-1..0, 0..W-1, ...: every rank's columns sum to the same index total, balancing the

@@ -6,7 +6,17 @@ Yardsticks on the same data, from the same process:
   (a) torch.tril + torch.linalg.solve_triangular — what tqr.lstsq does for its triangular solve —
       timed separately and together, with the bytes of the n x n temporary tril makes;
   (b) the existing tqr.lstsq (handle creation, prepare, apply, tril and solve per call).
-Usage: python tools/solve_bench.py [--reps N] [--no-torch] [m:b ...]"""
+Pipelined solve: every case also times tqr_solve_trsm_r (tqr.Solve) in both directions
+in the same run, with all `reps` timings of both kernels (`*_runs_ms`, restore copy subtracted) so the
+run-to-run spread can be read next to the difference; and per shape one "fused" record,
+tqr_lstsq_fused against tqr_lstsq_fused_solve on [A | B] with 64 right-hand sides (the restore copy of
+the whole [A | B] subtracted). Crossover measured on an MI355X (fp64): the pipelined call is 13.6 x
+faster at 16384^2, b = 256, nrhs = 64 (9.26 against 125.8 ms) and still 2.7 x faster with 64 strips
+(4096^2, nrhs = n), but 13 % slower with 256 strips (16384^2, nrhs = n: 153.8 against 136.2 ms), where
+the strips alone put two workgroups on every CU. Use it while the strips are fewer than the CUs (nrhs
+below about 64 x 256), tqr_trsm_r beyond; the crossover was not measured more finely.
+--solve-only skips the apply / lstsq split and the yardsticks (the two solves and the fused pair only).
+Usage: python tools/solve_bench.py [--reps N] [--no-torch] [--solve-only] [m:b ...]"""
 import json
 import os
 import sys
@@ -34,9 +44,54 @@ def torch_yardstick(A, X, n, reps):
         return f"unavailable ({type(e).__name__})"
 
 
+def timed_runs(fn, reps):
+    """device times (ms) of `reps` runs of fn() after one warm-up run, in run order"""
+    return [timed(fn, 1) if r == 0 else timed_once(fn) for r in range(reps)]
+
+
+def timed_once(fn):
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def fused_record(m, b, nrhs, reps):
+    """tqr_lstsq_fused and tqr_lstsq_fused_solve on the same [A | B] (n = m, one tile column of B)."""
+    import torch
+    n = m
+    AB0 = torch.empty((n + b, m), dtype=torch.float64, device="cuda")
+    tqr.fill_randzo(AB0, m, n + b, 5)
+    AB = AB0.clone()
+    tau = torch.zeros((n // b, m), dtype=torch.float64, device="cuda")
+    res = torch.zeros((nrhs,), dtype=torch.float64, device="cuda")
+    plan = tqr.TiledQR(m, n + b, b, torch.float64, steps=n // b)
+    sv = tqr.Solve(n, b, torch.float64, nrhs)
+    cs = torch.cuda.current_stream()
+
+    def run(solve):
+        def go():
+            AB.copy_(AB0)
+            plan.lstsq_fused(AB, tau, nrhs, res=res, stream=cs, solve=solve)
+        return go
+
+    t_copy = timed(lambda: AB.copy_(AB0), reps)
+    r0 = [round(t - t_copy, 3) for t in timed_runs(run(None), reps)]
+    r1 = [round(t - t_copy, 3) for t in timed_runs(run(sv), reps)]
+    plan.status()
+    sv.status()
+    return {"record": "fused", "dtype": "f64", "m": m, "n": n, "b": b, "nrhs": nrhs, "copy_ms": round(t_copy, 3),
+            "lstsq_fused_ms": min(r0), "lstsq_fused_runs_ms": r0,
+            "lstsq_fused_solve_ms": min(r1), "lstsq_fused_solve_runs_ms": r1}
+
+
 def main(argv):
     import torch
-    reps, use_torch, shapes = parse(argv)
+    solve_only = "--solve-only" in argv
+    reps, use_torch, shapes = parse([a for a in argv if a != "--solve-only"])
     assert torch.cuda.is_available(), "solve_bench.py measures on the GPU only"
     cs = torch.cuda.current_stream()
     for m, b in shapes:
@@ -47,8 +102,11 @@ def main(argv):
         plan = tqr.TiledQR(m, n, b, torch.float64)
         plan.execute(A, tau)
         plan.status()
-        ap = tqr.ApplyQ(m, n, b, torch.float64)
-        ap.prepare(A, tau, stream=cs)
+        ap = None
+        if not solve_only:
+            ap = tqr.ApplyQ(m, n, b, torch.float64)
+            ap.prepare(A, tau, stream=cs)
+        sv = tqr.Solve(n, b, torch.float64, n)
         for nrhs in (64, n):
             # the solves run in place on their own output again and again: a random X stays bounded
             # only if R is well conditioned, so every timed call starts from the same right-hand side
@@ -64,17 +122,31 @@ def main(argv):
                 return run
 
             t_copy = timed(lambda: X.copy_(X0), reps)
-            t_r = timed(fresh(lambda: tqr.trsm_r(A, X, b, trans=False, stream=cs)), reps) - t_copy
-            t_rt = timed(fresh(lambda: tqr.trsm_r(A, X, b, trans=True, stream=cs)), reps) - t_copy
+            runs = {}
+            for name, trans, solve in (("trsm_r", False, None), ("trsm_rt", True, None),
+                                       ("trsm_r_pipe", False, sv), ("trsm_rt_pipe", True, sv)):
+                ts = timed_runs(fresh(lambda: tqr.trsm_r(A, X, b, trans=trans, stream=cs, solve=solve)), reps)
+                runs[name] = [round(t - t_copy, 3) for t in ts]
+            sv.status(cs)
+            t_r, t_rt = min(runs["trsm_r"]), min(runs["trsm_rt"])
+            fl = float(n) * n * nrhs
+            pipe = {"trsm_r_pipe_ms": min(runs["trsm_r_pipe"]), "trsm_rt_pipe_ms": min(runs["trsm_rt_pipe"]),
+                    "gflops_r_pipe": round(fl / min(runs["trsm_r_pipe"]) / 1e6, 1),
+                    "gflops_rt_pipe": round(fl / min(runs["trsm_rt_pipe"]) / 1e6, 1),
+                    **{k + "_runs_ms": v for k, v in runs.items()}}
+            if solve_only:
+                print(json.dumps({"dtype": "f64", "m": m, "n": n, "b": b, "nrhs": nrhs, "copy_ms": round(t_copy, 3),
+                                  "trsm_r_ms": round(t_r, 3), "trsm_rt_ms": round(t_rt, 3), **pipe}), flush=True)
+                del X, X0, res
+                continue
             t_apply = timed(fresh(lambda: ap.apply(A, X, trans=True, stream=cs)), reps) - t_copy
             t_ls = timed(fresh(lambda: ap.lstsq(A, X, stream=cs)), reps) - t_copy
             t_lsr = timed(fresh(lambda: ap.lstsq(A, X, res=res, stream=cs)), reps) - t_copy
-            fl = float(n) * n * nrhs
             rec = {"dtype": "f64", "m": m, "n": n, "b": b, "nrhs": nrhs, "copy_ms": round(t_copy, 3),
                    "trsm_r_ms": round(t_r, 3), "trsm_rt_ms": round(t_rt, 3),
                    "gflops_r": round(fl / t_r / 1e6, 1), "gflops_rt": round(fl / t_rt / 1e6, 1),
                    "lstsq_ms": round(t_lsr, 3), "lstsq_apply_ms": round(t_apply, 3),
-                   "lstsq_solve_ms": round(t_ls - t_apply, 3), "lstsq_residual_ms": round(t_lsr - t_ls, 3)}
+                   "lstsq_solve_ms": round(t_ls - t_apply, 3), "lstsq_residual_ms": round(t_lsr - t_ls, 3), **pipe}
             if use_torch:
                 rec["yardstick_torch"] = torch_yardstick(A, X0, n, max(1, reps - 1))
                 try:
@@ -85,7 +157,9 @@ def main(argv):
                 rec["yardstick_torch"] = rec["yardstick_tqr_lstsq_ms"] = "skipped"
             print(json.dumps(rec), flush=True)
             del X, X0, res
-        del ap, plan, A, tau
+        del ap, sv, plan, A, tau
+        torch.cuda.empty_cache()
+        print(json.dumps(fused_record(m, b, 64, reps)), flush=True)
         torch.cuda.empty_cache()
 
 
