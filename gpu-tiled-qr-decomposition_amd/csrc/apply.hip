@@ -12,6 +12,8 @@
 // synchronisation is the __syncthreads() around the LDS staging of a group's V and T.
 // Every element of C is loaded and stored by one lane only (its column's lane with x = row mod
 // 4), so the head rows a step stores and the next step reloads are ordered by program order.
+// The device helpers of k_apply_q live in apply_dev.hpp and the handle in apply.hpp: apply_pipe.hip
+// runs the same tile operations with one workgroup per (strip, step) on them.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -19,30 +21,12 @@
 #include <mutex>
 #include <new>
 
+#include "apply.hpp"
+#include "apply_dev.hpp"
 #include "solve.hpp"
-#include "tiles.hpp"
 #include "tqr.h"
 
 namespace tqr {
-
-struct ApplyArgs {
-  const void* A;    // factorised matrix (S*): R, GEQRT V, TSQRT V_B
-  const void* tau;  // compact tau (S*), m x kmax (prepare only)
-  void* C;          // m x nrhs (S*)
-  double* Tw;       // T images: [(tile (l,k)) * NG + g][TIMG], tiles l >= k only
-  long lda, ldc;
-  int m, p, kmax, nrhs;
-};
-
-// index of tile (l,k), l >= k, among the stored tiles: panel k's p - k tiles follow panel k-1's
-__host__ __device__ inline size_t tile_slot(int l, int k, int p) {
-  return (size_t)((long long)k * p - (long long)k * (k - 1) / 2 + (l - k));
-}
-template <int B>
-__device__ __forceinline__ double* tg_ptr(const ApplyArgs& a, int l, int k, int g) {
-  using G = Geo<B>;
-  return a.Tw + (tile_slot(l, k, a.p) * G::NG + g) * G::TIMG;
-}
 
 // ---------------------------------------------------------------------------------------
 // prepare: T_g of every GEQRT tile (k,k) and TSQRT tile (l,k), row-major IB x TP images
@@ -76,99 +60,6 @@ __global__ __launch_bounds__(NT, 1) void k_apply_t(ApplyArgs a) {
   build_t<B>(Vs, tauv, Gs, Ts, Gp, ge ? c0 / 4 : 0);
   double* tg = tg_ptr<B>(a, l, k, g);
   for (int idx = threadIdx.x; idx < G::TSZ; idx += NT) tg[idx] = Ts[idx];
-}
-
-// ---------------------------------------------------------------------------------------
-// Strip / head traffic of C with ragged column counts: a lane whose column is >= nrhs (`on`
-// false) loads zeros and stores nothing. The accesses go through a buffer resource based at
-// the wave's first column of the row tile (wave-uniform, SGPRs) and one per-lane 32-bit byte
-// offset (tiles.hpp head_off; 16 columns: below 2^30 by the leading-dimension bound), as the
-// engine's *_buf helpers take them — a 64-bit pointer per lane and per tile costs the registers
-// the strip needs at b = 256. Default cache policy: nothing is handed to another workgroup, and
-// the head rows are re-read by the next tile of the step.
-// ---------------------------------------------------------------------------------------
-template <int B, typename S>
-__device__ __forceinline__ void load_rows(double (&X)[Geo<B>::NKS], __amdgpu_buffer_rsrc_t rs, unsigned off, bool on) {
-  if (on) {
-    load_strip_buf<B, S, 0>(X, rs, off, 0);
-  } else {
-#pragma unroll
-    for (int ks = 0; ks < Geo<B>::NKS; ++ks) X[ks] = 0.0;
-  }
-}
-template <int B, typename S>
-__device__ __forceinline__ void store_rows(const double (&X)[Geo<B>::NKS], __amdgpu_buffer_rsrc_t rs, unsigned off, bool on) {
-  if (on) store_strip_buf<B, S, 0>(X, rs, off, 0);
-}
-// Head rows of a group. REV (see stage_tq): register r of lane row x holds head row IB-1 - (4r + x)
-// = 4 (NRI-1-r) + (3 - x): `off` is then the offset of lane row 3 - x, and the registers swap ends.
-template <int B, typename S, bool REV>
-__device__ __forceinline__ void load_hrows(double (&H)[Geo<B>::NRI], __amdgpu_buffer_rsrc_t rs, unsigned off, bool on) {
-  constexpr int NRI = Geo<B>::NRI;
-  if (on) {
-    double t[NRI];
-    load_head_buf<B, S, 0>(t, rs, off);
-#pragma unroll
-    for (int r = 0; r < NRI; ++r) H[r] = t[REV ? NRI - 1 - r : r];
-  } else {
-#pragma unroll
-    for (int r = 0; r < NRI; ++r) H[r] = 0.0;
-  }
-}
-template <int B, typename S, bool REV>
-__device__ __forceinline__ void store_hrows(const double (&H)[Geo<B>::NRI], __amdgpu_buffer_rsrc_t rs, unsigned off, bool on) {
-  constexpr int NRI = Geo<B>::NRI;
-  if (on) {
-    double t[NRI];
-#pragma unroll
-    for (int r = 0; r < NRI; ++r) t[r] = H[REV ? NRI - 1 - r : r];
-    store_head_buf<B, S, 0>(t, rs, off);
-  }
-}
-// ---------------------------------------------------------------------------------------
-// The untransposed block reflector I - V T V^T (C <- Q C) on the unchanged apply_group of
-// tiles.hpp, which computes W = -M^T Z from the UPPER triangle of the T image M (k-blocks k2 <= wi):
-// Q needs W = -T Z, whose operand T^T is lower triangular. Relabel the group's IB reflectors in
-// reverse order (J = the reversal permutation): the images hold V' = V J and M = J T^T J, which is
-// upper triangular again, and the head rows are taken in reverse, H' = J H. Then Z' = H' + V'^T X =
-// J Z, W' = -M^T Z' = -J T Z = J W, H' + W' = J (H + W) and X + V' W' = X + V W: the same MFMA
-// stream and count as Q^T (no zero half of a full square), nothing new in tiles.hpp. REV selects it.
-// ---------------------------------------------------------------------------------------
-// T image of a group into LDS: as stored, or (REV) M[i][j] = T[IB-1-j][IB-1-i]
-template <int B, bool REV>
-__device__ __forceinline__ void stage_tq(double* Ts, const double* __restrict__ tg) {
-  using g = Geo<B>;
-  const __amdgpu_buffer_rsrc_t rs = uniform_rsrc(tg);
-  for (int idx = threadIdx.x; idx < g::IB * g::IB; idx += NT) {
-    const int r = idx / g::IB, c = idx % g::IB;
-    const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs, (unsigned)((r * g::TP + c) * sizeof(double)), 0, 0);
-    Ts[REV ? (g::IB - 1 - c) * g::TP + (g::IB - 1 - r) : r * g::TP + c] = dbl_of(v[0], v[1]);
-  }
-}
-// V image of group c0 / IB of a tile (tiles.hpp stage_v_ts / stage_v_ge: the same image; REV: its
-// columns in reverse order) read through a buffer resource based at the group's first column,
-// 32-bit offsets over its <= 32 columns (the leading-dimension bound) — per-lane 64-bit pointers
-// that advance with the tile loops cost the registers the strip needs at b = 256. GE: every
-// element of the tile column is loaded (R on and above the diagonal too: in range) and replaced
-// by the explicit unit-lower trapezoid's 0 / 1.
-template <int B, typename S, bool GE, bool REV>
-__device__ __forceinline__ void stage_vq(double* Vs, const S* __restrict__ vt, size_t ldm, int c0) {
-  using g = Geo<B>;
-  const __amdgpu_buffer_rsrc_t rs = uniform_rsrc(vt + (size_t)c0 * ldm);
-#pragma unroll 8
-  for (int idx = threadIdx.x; idx < B * g::IB; idx += NT) {
-    const int r = idx % B, c = idx / B, d = c0 + c;
-    const unsigned off = (unsigned)(((size_t)c * ldm + r) * sizeof(S));
-    double v;
-    if constexpr (sizeof(S) == 8) {
-      const auto u = __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0);
-      v = dbl_of(u[0], u[1]);
-    } else {
-      v = (double)__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
-    }
-    if (GE) v = r < d ? 0.0 : (r == d ? 1.0 : v);
-    Vs[r * g::VP + g::pc(REV ? g::IB - 1 - c : c)] = v;
-  }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -253,7 +144,6 @@ __global__ __launch_bounds__(NT, 2) void k_apply_q(ApplyArgs a) {
 // ---------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------
-typedef void (*afn)(ApplyArgs);
 template <int B, typename S>
 static void apply_kernels(afn* t, afn* qt, afn* qn) {
   *t = k_apply_t<B, S>;
@@ -275,31 +165,10 @@ static size_t timg_doubles(int b) {  // Geo<b>::TIMG
   return (ib * (ib + 1) + 127) / 128 * 128;
 }
 static_assert(Geo<256>::TIMG == 1152 && Geo<16>::TIMG == 384, "host timg_doubles mirrors Geo::TIMG");
-static bool apply_valid_b(int b) { return b == 16 || b == 32 || b == 64 || b == 128 || b == 256; }
-// the library's leading-dimension bound (include/tqr.h): 32 * ld * sizeof(element) < 2^31
-static bool apply_valid_ld(long ld, size_t es) { return ld > 0 && (size_t)32 * (size_t)ld * es <= 0x7fffffffull; }
 
 }  // namespace tqr
 
 using namespace tqr;
-
-// applies of one handle on up to NSLOT distinct streams are tracked one event each, so that a
-// later prepare can wait for all of them; further streams share slot 0 (and are ordered behind
-// its previous apply)
-static constexpr int APPLY_NSLOT = 8;
-
-struct tqr_apply {
-  int m, n, b, p, q, kmax, dtype;
-  size_t es, ws_bytes;
-  double* d_T = nullptr;
-  afn kt = nullptr, kqt = nullptr, kqn = nullptr;
-  bool prepared = false;
-  std::mutex mu;  // the enqueue sequences of prepare / apply_q (event bookkeeping)
-  hipEvent_t evPrep = nullptr;
-  hipEvent_t evApply[APPLY_NSLOT] = {};
-  hipStream_t slotStream[APPLY_NSLOT] = {};
-  int nslot = 0;  // slots holding an apply enqueued since the last prepare
-};
 
 #define HIPCHK(x)                                                                         \
   do {                                                                                    \
@@ -400,22 +269,15 @@ int tqr_apply_q(tqr_apply* ap, int trans, const void* dA, int ldda, void* dC, in
   hipStream_t cs = (hipStream_t)stream;
   std::lock_guard<std::mutex> lk(ap->mu);
   if (!ap->prepared) return TQR_EINVAL;
-  HIPCHK(hipStreamWaitEvent(cs, ap->evPrep, 0));
   int slot = 0;
-  while (slot < ap->nslot && ap->slotStream[slot] != cs) ++slot;
-  if (slot == APPLY_NSLOT) {  // more streams than slots: queue behind slot 0's apply and take it over
-    slot = 0;
-    HIPCHK(hipStreamWaitEvent(cs, ap->evApply[0], 0));
-  }
+  HIPCHK(apply_enqueue_begin(ap, cs, &slot));
   ApplyArgs a;
   a.A = dA; a.tau = nullptr; a.C = dC; a.Tw = ap->d_T; a.lda = ldda; a.ldc = lddc;
   a.m = ap->m; a.p = ap->p; a.kmax = ap->kmax; a.nrhs = nrhs;
   const unsigned grid = ((unsigned)nrhs + 63u) / 64u;
   hipLaunchKernelGGL(trans == TQR_TRANS ? ap->kqt : ap->kqn, dim3(grid), dim3(NT), lds_apply_q(ap->b), cs, a);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(ap->evApply[slot], cs));
-  ap->slotStream[slot] = cs;
-  if (slot == ap->nslot) ap->nslot = slot + 1;
+  HIPCHK(apply_enqueue_end(ap, cs, slot));
   return TQR_OK;
 }
 

@@ -1,0 +1,63 @@
+// Host side of the apply handle (include/tqr.h "apply"), shared by apply.hip (tqr_apply_*, tqr_lstsq)
+// and apply_pipe.hip (tqr_apply_pipe_*, tqr_lstsq_pipe): the handle itself, the argument checks, and
+// the event bookkeeping that orders every apply of a handle against its prepares.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+
+namespace tqr {
+
+struct ApplyArgs;
+typedef void (*afn)(ApplyArgs);
+
+static inline bool apply_valid_b(int b) { return b == 16 || b == 32 || b == 64 || b == 128 || b == 256; }
+// the library's leading-dimension bound (include/tqr.h): 32 * ld * sizeof(element) < 2^31
+static inline bool apply_valid_ld(long ld, size_t es) { return ld > 0 && (size_t)32 * (size_t)ld * es <= 0x7fffffffull; }
+
+// applies of one handle on up to NSLOT distinct streams are tracked one event each, so that a
+// later prepare can wait for all of them; further streams share slot 0 (and are ordered behind
+// its previous apply)
+constexpr int APPLY_NSLOT = 8;
+
+}  // namespace tqr
+
+struct tqr_apply {
+  int m, n, b, p, q, kmax, dtype;
+  size_t es, ws_bytes;
+  double* d_T = nullptr;
+  tqr::afn kt = nullptr, kqt = nullptr, kqn = nullptr;
+  bool prepared = false;
+  std::mutex mu;  // the enqueue sequences of prepare / apply_q (event bookkeeping)
+  hipEvent_t evPrep = nullptr;
+  hipEvent_t evApply[tqr::APPLY_NSLOT] = {};
+  hipStream_t slotStream[tqr::APPLY_NSLOT] = {};
+  int nslot = 0;  // slots holding an apply enqueued since the last prepare
+};
+
+namespace tqr {
+
+// Around the launch of an apply on stream cs, ap->mu held and ap prepared. begin: cs waits for the
+// handle's last prepare, and *slot is the event slot of cs. end: the apply is recorded in that slot,
+// so that the next prepare waits for it.
+static inline hipError_t apply_enqueue_begin(tqr_apply* ap, hipStream_t cs, int* slot) {
+  hipError_t e = hipStreamWaitEvent(cs, ap->evPrep, 0);
+  if (e != hipSuccess) return e;
+  int s = 0;
+  while (s < ap->nslot && ap->slotStream[s] != cs) ++s;
+  if (s == APPLY_NSLOT) {  // more streams than slots: queue behind slot 0's apply and take it over
+    s = 0;
+    e = hipStreamWaitEvent(cs, ap->evApply[0], 0);
+  }
+  *slot = s;
+  return e;
+}
+static inline hipError_t apply_enqueue_end(tqr_apply* ap, hipStream_t cs, int slot) {
+  const hipError_t e = hipEventRecord(ap->evApply[slot], cs);
+  if (e != hipSuccess) return e;
+  ap->slotStream[slot] = cs;
+  if (slot == ap->nslot) ap->nslot = slot + 1;
+  return hipSuccess;
+}
+
+}  // namespace tqr

@@ -1,0 +1,416 @@
+// The apply of Q / Q^T spread over workgroups (include/tqr.h "pipelined apply"): the same tile
+// operations as apply.hip's k_apply_q on the same operands in the same order, hence the same bits —
+// but one workgroup per (64-column strip, step k) instead of one per strip, so a narrow C uses up to
+// kmax CUs, not one.
+//
+// k_apply_q is a two-dimensional wavefront over (step k, row tile l): UNMQR(k) on C_k, then
+// TSMQR(l, k) on [C_k; C_l] for l = k+1 .. p-1 (Q^T; the exact reverse for Q). Operation (k, l) needs
+// C_k as (k, l-1) left it and C_l as step k-1 (Q: k+1) left it; nothing else touches those rows in
+// between. k_apply_q_pipe gives step k of a strip to one workgroup, which runs k_apply_q's own unmqr /
+// tsmqr — apply_dev.hpp's images, tiles.hpp's apply_group, group by group, the head rows of C_k loaded
+// and stored per group through memory — and waits for C_l row tile by row tile:
+//   Q^T, step k:  [wait (k-1, k)]  UNMQR(k);  l = k+1 .. p-1:  [wait (k-1, l)]  TSMQR(l, k)  publish (k, l)
+//   Q,   step k:  l = p-1 .. k+1:  [wait (k+1, l)]  TSMQR(l, k)  publish (k, l);  UNMQR(k)  publish (k, k)
+// (no wait in the first step of a direction: k = 0, or k = kmax-1). Flag (k, l) says "step k is done
+// with C_l"; (k, k), used by Q only, "step k's UNMQR is done", which is when C_k is final for step k-1.
+// Every row tile therefore receives the operations of k_apply_q in k_apply_q's order, and passes
+// through memory between two of them exactly where it does there (fp32 storage: rounded to float at
+// every store), so the critical path is about p + 2 kmax tile operations instead of all of them.
+//
+// Protocol between workgroups (MI355X_MICROARCH.md "Workgroup dispatch ... inter-workgroup
+// visibility", "Valid forms", first table row; solve_pipe.hip's form):
+//   * work items come from one atomic ticket counter, never from blockIdx: ticket t is (strip, step)
+//     by apply_ticket_map, and the only producer of (strip, k), which is (strip, k-1) for Q^T and
+//     (strip, k+1) for Q, has a smaller ticket. A workgroup that waits holds a ticket, so what it waits
+//     for was taken by a workgroup already running, whatever the dispatch order and however few
+//     workgroups are resident;
+//   * every load and store of C in this kernel is an sc1 buffer access (L1-bypassing / write-through),
+//     the workgroup's own rows included: every byte of C was stored or will be loaded by another
+//     workgroup. V, T and tau come from earlier launches: plain loads. To publish, each wave drains
+//     (s_waitcnt vmcnt(0)), the workgroup meets at a barrier, and one lane stores the flag (sc1). A
+//     consumer's thread 0 polls the flag with sc1 loads and s_sleep; the other waves load the row tile
+//     only behind the barrier thread 0 then joins;
+//   * the table row holds at one workgroup per CU: the launch asks for PIPE_LDS bytes of LDS;
+//   * a flag holds the epoch of the call that set it and a call waits for its own epoch, so nothing
+//     is reset between calls; the ticket counter is zeroed by a memset ahead of each launch, and the
+//     calls of one handle are serialised by an event;
+//   * every spin is bounded (PIPE_TIMEOUT): on expiry the error word is set, the workgroup leaves
+//     without publishing, and every workgroup that sees the word — in a spin or before it takes a
+//     ticket — leaves too. tqr_apply_pipe_status reports it.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <new>
+
+#include "apply.hpp"
+#include "apply_dev.hpp"
+#include "pipe_dev.hpp"
+#include "solve.hpp"
+#include "tqr.h"
+
+namespace tqr {
+
+// Work item of ticket t on kmax steps x nstrips strips: tickets go step by step in the order the
+// apply needs them (Q^T: step 0 first; Q: step kmax-1 first), all strips of a step side by side — so
+// the producer of (strip, step), the step before it in the same strip, has a smaller ticket.
+__host__ __device__ inline void apply_ticket_map(int kmax, int nstrips, bool trans, int t, int* strip, int* step) {
+  const int pos = t / nstrips;
+  *strip = t - pos * nstrips;
+  *step = trans ? pos : kmax - 1 - pos;
+}
+
+struct ApplyPipeArgs {
+  ApplyArgs q;      // k_apply_q's arguments (tau unused)
+  long long nslot;  // flags per strip: the stored tiles (l,k), l >= k, k < kmax
+  int epoch;        // this call's flag value
+  int* ws;          // the handle's workspace: header, then the flags [strip][tile_slot(l, k, p)]
+};
+
+// ---------------------------------------------------------------------------------------
+// One workgroup per ticket = (strip, step k): wave w owns columns 64 strip + 16w .. + 15 of C, a lane
+// its column's rows x mod 4, as in k_apply_q. A wave with no column below nrhs does no MFMA work but
+// takes part in the staging and in every barrier.
+// ---------------------------------------------------------------------------------------
+template <int B, typename S, bool TRANS>
+__global__ __launch_bounds__(NT) void k_apply_q_pipe(ApplyPipeArgs pa) {
+  using G = Geo<B>;
+  constexpr int IB = G::IB, NG = G::NG;
+  constexpr int SC1 = 16;  // aux bits of every C access
+  extern __shared__ __align__(16) double lds[];
+  double* Vs = lds;
+  double* Ts = Vs + G::VSZ;
+  __shared__ int s_tk, s_ok;
+  const ApplyArgs& a = pa.q;
+
+  if (threadIdx.x == 0)
+    s_tk = ld_sc1(pa.ws + PIPE_ERR) ? -1 : __hip_atomic_fetch_add((pint*)(pa.ws + PIPE_TICKET), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  const int tk = __builtin_amdgcn_readfirstlane(s_tk), nstrips = (a.nrhs + 63) >> 6;
+  if (tk < 0 || tk >= a.kmax * nstrips) return;  // (an earlier call of the handle timed out: tqr_apply_pipe_status)
+  int strip, k;
+  apply_ticket_map(a.kmax, nstrips, TRANS, tk, &strip, &k);
+
+  const size_t ldc = a.ldc;
+  const int lane = threadIdx.x & 63, x = lane >> 4, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int col0 = strip * 64 + 16 * w, col = col0 + (lane & 15);
+  const bool active = col0 < a.nrhs;  // wave-uniform
+  // The staging and the MFMA loops leave few SGPRs at b = 256, so what only the hand-over reads sits
+  // in VGPRs, which are plentiful at one workgroup per CU (solve_pipe.hip): the lane's column mask as
+  // an integer instead of a mask pair, the strip's flags, the error word and the epoch.
+  int on = col < a.nrhs;
+  unsigned long long flv = (unsigned long long)(pa.ws + PIPE_HDR) + (unsigned long long)strip * (unsigned long long)pa.nslot * sizeof(int);
+  unsigned long long errv = (unsigned long long)(pa.ws + PIPE_ERR);
+  int epoch = pa.epoch, nact = a.nrhs - col0;
+  asm volatile("" : "+v"(on), "+v"(flv), "+v"(errv), "+v"(epoch), "+v"(nact));
+  // So do the operands' addresses, which the staging turns into wave-uniform resources by readfirstlane
+  // (uniform_rsrc) once per group: tile column k of A, its leading dimension, and the T images.
+  unsigned long long akv = (unsigned long long)((const S*)a.A + (size_t)k * B * (size_t)a.lda), ldav = (unsigned long long)a.lda;
+  unsigned long long twv = (unsigned long long)a.Tw;
+  asm volatile("" : "+v"(akv), "+v"(ldav), "+v"(twv));
+  const S* const Ak = (const S*)akv;
+  const size_t lda = ldav;
+  ApplyArgs at = a;  // (tg_ptr reads Tw and p)
+  at.Tw = (double*)twv;
+  // one resource over the wave's 16 columns of C (an idle wave's is never used); a row tile is a byte
+  // offset in it (below 2^31 by the leading-dimension bound), koff the workgroup's own C_k
+  S* Cw = (S*)a.C + (size_t)(active ? col0 : 0) * ldc;
+  const __amdgpu_buffer_rsrc_t rc = uniform_rsrc(Cw);
+  const unsigned coff = head_off<B, S>(ldc, 0);
+  const unsigned koff = coff + (unsigned)k * (unsigned)(B * sizeof(S));
+  double X[G::NKS];
+  double H[G::NRI];
+
+  // Flags, as pointers indexed by the row tile l: fmine[l] is this step's (k, l) — slot tile_slot(k, k, p)
+  // + l - k — and fprod[l] the producing step's (k', l), k' = k - 1 (Q^T) or k + 1 (Q); the first step
+  // of a direction has no producer. Parked in VGPRs like the rest of the hand-over's values.
+  constexpr int KP = TRANS ? -1 : 1;
+  const bool first = TRANS ? k == 0 : k == a.kmax - 1;
+  unsigned long long fmine = flv + (unsigned long long)((long long)tile_slot(k, k, a.p) - k) * sizeof(int);
+  // (computed in the first step too, where k + KP is no step and the pointer is never used: a select
+  // here kept `first` in a mask pair of SGPRs)
+  unsigned long long fprod = flv + (unsigned long long)((long long)tile_slot(k + KP, k + KP, a.p) - (k + KP)) * sizeof(int);
+  asm volatile("" : "+v"(fmine), "+v"(fprod));
+  // all threads: the producing step has released row tile l of this strip in this call (false: error
+  // or timeout, uniform)
+  auto wait = [&](int l) {
+    if (threadIdx.x == 0) s_ok = pipe_spin_ge((int*)fprod + l, epoch, (int*)errv) ? 1 : 0;
+    __syncthreads();
+    // (thread 0 rewrites s_ok only behind the next barrier, which every thread reaches after this read)
+    return s_ok != 0;
+  };
+  // release row tile l: every wave's stores drained, a barrier, one lane's flag store
+  auto publish = [&](int l) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store((pint*)((int*)fmine + l), epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  // k_apply_q's unmqr(k): tile (k,k) on C_k, groups ascending (Q^T) / descending (Q)
+  auto unmqr = [&](const bool active) {
+    const S* Vt = Ak + (size_t)k * B;
+    if (active) load_rows<B, S, SC1>(X, rc, koff, on != 0);
+    for (int gi = 0; gi < NG; ++gi) {
+      const int g = TRANS ? gi : NG - 1 - gi;
+      __syncthreads();
+      stage_vq<B, S, true, !TRANS>(Vs, Vt, lda, g * IB);
+      stage_tq<B, !TRANS>(Ts, tg_ptr<B>(at, k, k, g));
+      __syncthreads();
+      if (active) apply_group<B, false>(Vs, Ts, X, H, g * IB / 4);
+    }
+    if (active) store_rows<B, S, SC1>(X, rc, koff, on != 0);
+  };
+  // k_apply_q's tsmqr(l, k): tile (l,k) on [C_k; C_l] — C_l's strip stays in registers over the groups,
+  // the 32 head rows of C_k are loaded and stored per group
+  auto tsmqr = [&](int l) {
+    const S* Vt = Ak + (size_t)l * B;
+    const unsigned loff = coff + (unsigned)l * (unsigned)(B * sizeof(S));
+    if (active) load_rows<B, S, SC1>(X, rc, loff, on != 0);
+    for (int gi = 0; gi < NG; ++gi) {
+      const int g = TRANS ? gi : NG - 1 - gi;
+      __syncthreads();
+      stage_vq<B, S, false, !TRANS>(Vs, Vt, lda, g * IB);
+      stage_tq<B, !TRANS>(Ts, tg_ptr<B>(at, l, k, g));
+      __syncthreads();
+      if (active) {
+        // (Q: the head rows in reverse — this lane takes the rows of lane row 3 - x)
+        const unsigned hoff = koff + (unsigned)((g * IB + (TRANS ? 0 : 3 - 2 * x)) * (int)sizeof(S));
+        load_hrows<B, S, !TRANS, SC1>(H, rc, hoff, on != 0);
+        apply_group<B, true>(Vs, Ts, X, H, 0);
+        store_hrows<B, S, !TRANS, SC1>(H, rc, hoff, on != 0);
+      }
+    }
+    if (active) store_rows<B, S, SC1>(X, rc, loff, on != 0);
+  };
+
+  // No byte of a row tile other than C_k is read before its flag is seen: the only such loads are
+  // tsmqr's load_rows, behind wait. C_k itself was last stored by the producing step as its C_l, l = k
+  // (Q^T: flag (k-1, k), awaited ahead of unmqr; Q: by nobody).
+  if constexpr (TRANS) {
+    if (!first && !wait(k)) return;
+    unmqr(active);
+    for (int l = k + 1; l < a.p; ++l) {
+      if (!first && !wait(l)) return;
+      tsmqr(l);
+      publish(l);
+    }
+  } else {
+    for (int l = a.p - 1; l > k; --l) {
+      if (!first && !wait(l)) return;  // (l = k+1: flag (k+1, k+1), the producer's UNMQR)
+      tsmqr(l);
+      publish(l);
+    }
+    // (`active` anew from its parked operand: as one value it would have to outlive the loop above, a
+    // lane-mask pair of SGPRs that spilled at b = 256)
+    asm volatile("" : "+v"(nact));
+    unmqr(__builtin_amdgcn_readfirstlane(nact) > 0);
+    publish(k);
+  }
+}
+
+typedef void (*apfn)(ApplyPipeArgs);
+template <int B>
+static apfn apipe_kernel(int dtype, int trans) {
+  if (dtype == TQR_F64) return trans == TQR_TRANS ? k_apply_q_pipe<B, double, true> : k_apply_q_pipe<B, double, false>;
+  return trans == TQR_TRANS ? k_apply_q_pipe<B, float, true> : k_apply_q_pipe<B, float, false>;
+}
+static apfn apipe_kernel_b(int b, int dtype, int trans) {
+  switch (b) {
+    case 16: return apipe_kernel<16>(dtype, trans);
+    case 32: return apipe_kernel<32>(dtype, trans);
+    case 64: return apipe_kernel<64>(dtype, trans);
+    case 128: return apipe_kernel<128>(dtype, trans);
+    default: return apipe_kernel<256>(dtype, trans);
+  }
+}
+
+#define HIPCHK(x)                                                                         \
+  do {                                                                                    \
+    hipError_t e_ = (x);                                                                  \
+    if (e_ != hipSuccess) {                                                               \
+      fprintf(stderr, "tqr: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); \
+      return TQR_EHIP;                                                                    \
+    }                                                                                     \
+  } while (0)
+
+}  // namespace tqr
+
+using namespace tqr;
+
+struct tqr_apply_pipe {
+  int m, n, b, p, kmax, dtype, nrhs_max;
+  size_t es, ws_bytes;
+  long long nslot;  // flags per strip
+  apfn kn = nullptr, kt = nullptr;
+  std::mutex mu;        // the enqueue sequence of a call (epoch, event bookkeeping)
+  int* d_ws = nullptr;  // device workspace (null until a gfx950 was seen)
+  hipEvent_t evDone = nullptr;
+  int epoch = 0;
+};
+
+// The handle's device side, made on first need (tqr_apply_pipe_create where a device is present): the
+// zeroed workspace, the event and the kernels' LDS attribute. mu held, or the handle not yet shared.
+static int apply_pipe_ready(tqr_apply_pipe* pp) {
+  if (pp->d_ws) return TQR_OK;
+  int dev = 0;
+  hipDeviceProp_t pr;
+  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) {
+    (void)hipGetLastError();
+    return TQR_ENODEV;
+  }
+  if (strncmp(pr.gcnArchName, "gfx950", 6) != 0) {
+    fprintf(stderr, "tqr: device %d is %s, this build targets gfx950 only\n", dev, pr.gcnArchName);
+    return TQR_ENODEV;
+  }
+  HIPCHK(hipFuncSetAttribute((const void*)pp->kn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS));
+  HIPCHK(hipFuncSetAttribute((const void*)pp->kt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS));
+  if (!pp->evDone) HIPCHK(hipEventCreateWithFlags(&pp->evDone, hipEventDisableTiming));
+  int* ws = nullptr;
+  if (hipMalloc(&ws, pp->ws_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return TQR_ENOMEM;
+  }
+  if (hipMemset(ws, 0, pp->ws_bytes) != hipSuccess) {
+    (void)hipFree(ws);
+    return TQR_EHIP;
+  }
+  pp->d_ws = ws;
+  return TQR_OK;
+}
+
+// tqr_apply_pipe_q's argument errors (everything but the handle's prepared state, which needs ap->mu)
+static bool apply_pipe_args_ok(const tqr_apply_pipe* pp, const tqr_apply* ap, int trans, const void* dA, int ldda,
+                               const void* dC, int nrhs, int lddc) {
+  return pp && ap && dA && dC && (trans == TQR_NOTRANS || trans == TQR_TRANS) && nrhs >= 1 && nrhs <= pp->nrhs_max &&
+         ldda >= pp->m && lddc >= pp->m && apply_valid_ld(ldda, pp->es) && apply_valid_ld(lddc, pp->es) && ap->m == pp->m &&
+         ap->n == pp->n && ap->b == pp->b && ap->dtype == pp->dtype;
+}
+
+extern "C" {
+
+int tqr_apply_pipe_ticket(int kmax, int nstrips, int trans, int ticket, int* strip, int* step) {
+  if (kmax < 1 || nstrips < 1 || (trans != TQR_NOTRANS && trans != TQR_TRANS) || !strip || !step || ticket < 0 ||
+      (long long)ticket >= (long long)kmax * nstrips)
+    return TQR_EINVAL;
+  apply_ticket_map(kmax, nstrips, trans == TQR_TRANS, ticket, strip, step);
+  return TQR_OK;
+}
+
+void tqr_apply_pipe_destroy(tqr_apply_pipe* pp) {
+  if (!pp) return;
+  if (pp->evDone) {
+    (void)hipEventSynchronize(pp->evDone);  // the last call may still be reading the workspace
+    (void)hipEventDestroy(pp->evDone);
+  }
+  if (pp->d_ws) (void)hipFree(pp->d_ws);
+  delete pp;
+}
+
+int tqr_apply_pipe_create(tqr_apply_pipe** out, int m, int n, int b, int dtype, int nrhs_max) {
+  if (!out) return TQR_EINVAL;
+  *out = nullptr;
+  if (!apply_valid_b(b) || m <= 0 || n <= 0 || m % b || n % b || (dtype != TQR_F32 && dtype != TQR_F64) ||
+      !apply_valid_ld(m, dtype == TQR_F64 ? 8 : 4) || nrhs_max < 1)
+    return TQR_EINVAL;
+  const int p = m / b, q = n / b, kmax = p < q ? p : q;
+  const size_t nstrips = ((size_t)nrhs_max + 63) / 64, items = nstrips * (size_t)kmax;
+  if (items > 0x7fffffffull) return TQR_EINVAL;  // (one workgroup per item: the grid)
+  tqr_apply_pipe* pp = new (std::nothrow) tqr_apply_pipe();
+  if (!pp) return TQR_ENOMEM;
+  pp->m = m; pp->n = n; pp->b = b; pp->p = p; pp->kmax = kmax; pp->dtype = dtype; pp->nrhs_max = nrhs_max;
+  pp->es = dtype == TQR_F64 ? 8 : 4;
+  pp->nslot = (long long)tile_slot(kmax, kmax, p);
+  pp->ws_bytes = ((size_t)PIPE_HDR + nstrips * (size_t)pp->nslot) * sizeof(int);
+  pp->kn = apipe_kernel_b(b, dtype, TQR_NOTRANS);
+  pp->kt = apipe_kernel_b(b, dtype, TQR_TRANS);
+  // without a gfx950 the handle exists but holds no device memory: every call on it validates its
+  // arguments and then returns TQR_ENODEV
+  const int st = apply_pipe_ready(pp);
+  if (st != TQR_OK && st != TQR_ENODEV) {
+    tqr_apply_pipe_destroy(pp);
+    return st;
+  }
+  *out = pp;
+  return TQR_OK;
+}
+
+size_t tqr_apply_pipe_workspace_bytes(const tqr_apply_pipe* pp) { return pp ? pp->ws_bytes : 0; }
+
+int tqr_apply_pipe_q(tqr_apply_pipe* pp, tqr_apply* ap, int trans, const void* dA, int ldda, void* dC, int nrhs,
+                     int lddc, void* stream) {
+  if (!apply_pipe_args_ok(pp, ap, trans, dA, ldda, dC, nrhs, lddc)) return TQR_EINVAL;
+  hipStream_t cs = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lp(pp->mu);  // (always pp's before ap's)
+  std::lock_guard<std::mutex> la(ap->mu);
+  if (!ap->prepared) return TQR_EINVAL;
+  if (const int st = apply_pipe_ready(pp)) return st;
+  HIPCHK(hipStreamWaitEvent(cs, pp->evDone, 0));  // the previous call of this handle (any stream)
+  if (pp->epoch == INT_MAX) {  // the epochs start over: behind the previous call, ahead of this one
+    HIPCHK(hipMemsetAsync(pp->d_ws + PIPE_HDR, 0, pp->ws_bytes - PIPE_HDR * sizeof(int), cs));
+    pp->epoch = 0;
+  }
+  int slot = 0;
+  HIPCHK(apply_enqueue_begin(ap, cs, &slot));
+  ApplyPipeArgs a;
+  a.q.A = dA; a.q.tau = nullptr; a.q.C = dC; a.q.Tw = ap->d_T; a.q.lda = ldda; a.q.ldc = lddc;
+  a.q.m = pp->m; a.q.p = pp->p; a.q.kmax = pp->kmax; a.q.nrhs = nrhs;
+  a.nslot = pp->nslot;
+  a.epoch = pp->epoch + 1;
+  a.ws = pp->d_ws;
+  const unsigned grid = (unsigned)((nrhs + 63) / 64) * (unsigned)pp->kmax;
+  HIPCHK(hipMemsetAsync(pp->d_ws + PIPE_TICKET, 0, sizeof(int), cs));  // (the error word stays: tqr_apply_pipe_status)
+  hipLaunchKernelGGL(trans == TQR_TRANS ? pp->kt : pp->kn, dim3(grid), dim3(NT), PIPE_LDS, cs, a);
+  const hipError_t le = hipGetLastError();
+  // recorded behind whatever was enqueued, so the next call and the next prepare stay ordered after it
+  const hipError_t re = hipEventRecord(pp->evDone, cs);
+  const hipError_t ae = apply_enqueue_end(ap, cs, slot);
+  HIPCHK(le);
+  pp->epoch = a.epoch;  // committed once the launch is enqueued
+  HIPCHK(re);
+  HIPCHK(ae);
+  return TQR_OK;
+}
+
+int tqr_apply_pipe_status(tqr_apply_pipe* pp, void* stream) {
+  if (!pp) return TQR_EINVAL;
+  std::lock_guard<std::mutex> lk(pp->mu);
+  if (!pp->d_ws) return TQR_OK;  // nothing was ever enqueued
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  HIPCHK(hipEventSynchronize(pp->evDone));  // the handle's last call, whatever its stream
+  int err = 0;
+  HIPCHK(hipMemcpy(&err, pp->d_ws + PIPE_ERR, sizeof(int), hipMemcpyDeviceToHost));
+  if (!err) return TQR_OK;
+  fprintf(stderr, "tqr: pipelined apply: a wait for another workgroup's row tile timed out (error word %d)\n", err);
+  HIPCHK(hipMemset(pp->d_ws + PIPE_ERR, 0, sizeof(int)));  // reported once; the handle is usable again
+  return TQR_EHIP;
+}
+
+// tqr_lstsq (apply.hip) with the pipelined apply and the pipelined solve in place of tqr_apply_q and
+// tqr_trsm_r: the same steps in the same order on `stream`, nothing allocated
+int tqr_lstsq_pipe(tqr_apply_pipe* pp, tqr_solve* sv, tqr_apply* ap, int trans, const void* dA, int ldda, void* dB,
+                   int nrhs, int lddb, void* dres, void* stream) {
+  if (!pp || !sv || !ap) return TQR_EINVAL;
+  if (!apply_pipe_args_ok(pp, ap, trans, dA, ldda, dB, nrhs, lddb) || ap->m < ap->n) return TQR_EINVAL;
+  const SolveShape ss = solve_shape(sv);
+  if (ss.n != ap->n || ss.b != ap->b || ss.dtype != ap->dtype || nrhs > ss.nrhs_max) return TQR_EINVAL;
+  {
+    std::lock_guard<std::mutex> lk(ap->mu);
+    if (!ap->prepared) return TQR_EINVAL;
+  }
+  int st;
+  if (trans == TQR_NOTRANS) {
+    // B <- Q^T B; rows 0 .. n-1 <- R^{-1} of them; the residual norms from rows n .. m-1
+    if ((st = tqr_apply_pipe_q(pp, ap, TQR_TRANS, dA, ldda, dB, nrhs, lddb, stream)) != TQR_OK) return st;
+    if ((st = tqr_solve_trsm_r(sv, TQR_NOTRANS, dA, ldda, dB, nrhs, lddb, stream)) != TQR_OK) return st;
+    return dres ? resnorm(ap->dtype, dB, lddb, ap->n, ap->m, nrhs, dres, stream) : TQR_OK;
+  }
+  // x = Q [R^{-T} c; 0]
+  if (ap->m > ap->n)
+    HIPCHK(hipMemset2DAsync((char*)dB + (size_t)ap->n * ap->es, (size_t)lddb * ap->es, 0, (size_t)(ap->m - ap->n) * ap->es,
+                            (size_t)nrhs, (hipStream_t)stream));
+  if ((st = tqr_solve_trsm_r(sv, TQR_TRANS, dA, ldda, dB, nrhs, lddb, stream)) != TQR_OK) return st;
+  return tqr_apply_pipe_q(pp, ap, TQR_NOTRANS, dA, ldda, dB, nrhs, lddb, stream);
+}
+
+}  // extern "C"

@@ -3,6 +3,7 @@
 #pragma once
 
 struct tqr_plan;
+struct tqr_solve;
 
 namespace tqr {
 
@@ -17,5 +18,11 @@ struct PlanShape {
   bool capped;
 };
 PlanShape plan_shape(const tqr_plan* pl);
+
+// What a pipelined-solve handle was created for (solve_pipe.hip; read by apply_pipe.hip's tqr_lstsq_pipe).
+struct SolveShape {
+  int n, b, dtype, nrhs_max;
+};
+SolveShape solve_shape(const tqr_solve* sv);
 
 }  // namespace tqr

@@ -37,6 +37,7 @@
 #include <mutex>
 #include <new>
 
+#include "pipe_dev.hpp"
 #include "solve.hpp"
 #include "solve_dev.hpp"
 #include "tqr.h"
@@ -61,34 +62,8 @@ struct PipeArgs {
   int* ws;       // the handle's workspace (one pointer: the kernels are short of SGPRs at b = 256)
 };
 
-// workspace (ints): the ticket counter, the error word, padding to a 128-B line, then the flags
-// [strip][row] = the epoch of the call whose X_row of the strip is final
-constexpr int PIPE_TICKET = 0, PIPE_ERR = 1, PIPE_HDR = 32;
-// dynamic LDS of a launch: more than half of a CU's 160 KiB, whatever the operand image needs
-constexpr size_t PIPE_LDS = 96 * 1024;
-static_assert(PIPE_LDS >= Geo<256>::VSZ * sizeof(double) && 2 * PIPE_LDS > 160 * 1024, "one workgroup per CU");
-constexpr unsigned long long PIPE_TIMEOUT = 500000000ull;  // 5 s of s_memrealtime (100 MHz), as FLOW_TIMEOUT
-
-// (global-address-space accesses: a generic pointer would make them FLAT instructions, flow.hpp)
-typedef __attribute__((address_space(1))) int pint;
-__device__ __forceinline__ int ld_sc1(int* p) {
-  return __hip_atomic_load((pint*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// thread 0 only: spin until *p >= target; false on error / timeout (flow.hpp spin_ge_i; inlined: a call
-// here made the kernel keep wave-uniform values in VGPR lanes across it)
-__device__ __forceinline__ bool pipe_spin_ge(int* p, int target, int* err) {
-  if (ld_sc1(p) >= target) return true;
-  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-  while (ld_sc1(p) < target) {
-    if (ld_sc1(err)) return false;
-    __builtin_amdgcn_s_sleep(8);
-    if (__builtin_amdgcn_s_memrealtime() - t0 > PIPE_TIMEOUT) {
-      __hip_atomic_store((pint*)err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      return false;
-    }
-  }
-  return true;
-}
+// workspace (pipe_dev.hpp): the header, then the flags [strip][row] = the epoch of the call whose X_row
+// of the strip is final
 
 // ---------------------------------------------------------------------------------------
 // One workgroup per ticket = (strip, tile row i): wave w owns columns 64 strip + 16w .. + 15 of X.
@@ -293,6 +268,10 @@ static int solve_pipe_ready(tqr_solve* sv) {
   sv->d_ws = ws;
   return TQR_OK;
 }
+
+namespace tqr {
+SolveShape solve_shape(const tqr_solve* sv) { return {sv->n, sv->b, sv->dtype, sv->nrhs_max}; }
+}  // namespace tqr
 
 extern "C" {
 

@@ -125,6 +125,20 @@ def lib():
     L.tqr_solve_ticket.restype = _I
     L.tqr_lstsq_fused_solve.argtypes = [_P, _P, _P, _I, _P, _I, _P, _P]
     L.tqr_lstsq_fused_solve.restype = _I
+    L.tqr_apply_pipe_create.argtypes = [ctypes.POINTER(_P), _I, _I, _I, _I, _I]
+    L.tqr_apply_pipe_create.restype = _I
+    L.tqr_apply_pipe_workspace_bytes.argtypes = [_P]
+    L.tqr_apply_pipe_workspace_bytes.restype = ctypes.c_size_t
+    L.tqr_apply_pipe_q.argtypes = [_P, _P, _I, _P, _I, _P, _I, _I, _P]
+    L.tqr_apply_pipe_q.restype = _I
+    L.tqr_apply_pipe_status.argtypes = [_P, _P]
+    L.tqr_apply_pipe_status.restype = _I
+    L.tqr_apply_pipe_destroy.argtypes = [_P]
+    L.tqr_apply_pipe_destroy.restype = None
+    L.tqr_apply_pipe_ticket.argtypes = [_I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]
+    L.tqr_apply_pipe_ticket.restype = _I
+    L.tqr_lstsq_pipe.argtypes = [_P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P]
+    L.tqr_lstsq_pipe.restype = _I
     _lib = L
     return L
 
@@ -492,25 +506,42 @@ class ApplyQ:
         ldda = ldda or A.shape[-1]
         check(lib().tqr_apply_prepare(self.h, _ptr(A), ldda, _ptr(tau), _stream_handle(stream)), "tqr_apply_prepare")
 
-    def apply(self, A, C, trans=True, nrhs=None, ldda=None, lddc=None, stream=None):
+    def apply(self, A, C, trans=True, nrhs=None, ldda=None, lddc=None, stream=None, pipe=None):
         """C (nrhs, lddc) <- Q^T C (trans) or Q C, in place; A as given to prepare(). nrhs, ldda and
-        lddc default to the tensors' shapes. Stream-ordered."""
+        lddc default to the tensors' shapes. Stream-ordered. pipe: an ApplyPipe handle made for this
+        (m, n, b, dtype) — the same bits from the pipelined kernel (ApplyPipe.apply), for a narrow C."""
+        if pipe is not None:
+            return pipe.apply(self, A, C, trans=trans, nrhs=nrhs, ldda=ldda, lddc=lddc, stream=stream)
         ldda = ldda or A.shape[-1]
         lddc = lddc or C.shape[-1]
         nrhs = C.shape[0] if nrhs is None else nrhs
         check(lib().tqr_apply_q(self.h, 1 if trans else 0, _ptr(A), ldda, _ptr(C), nrhs, lddc, _stream_handle(stream)),
               "tqr_apply_q")
 
-    def lstsq(self, A, B, trans=False, nrhs=None, ldda=None, lddb=None, res=None, stream=None):
+    def lstsq(self, A, B, trans=False, nrhs=None, ldda=None, lddb=None, res=None, stream=None, pipe=None, solve=None):
         """tqr_lstsq on a prepared handle with m >= n; A as given to prepare(), B (nrhs, lddb) in place.
         trans=False: least squares — B <- Q^T B, then rows 0 .. n-1 <- X; `res` (optional, nrhs
         elements of B's dtype) receives |A x - b| per column. trans=True: the minimum-norm solution of
-        A^T x = c, c in rows 0 .. n-1 of B on entry, x in all m rows on exit. Stream-ordered."""
+        A^T x = c, c in rows 0 .. n-1 of B on entry, x in all m rows on exit. Stream-ordered.
+        pipe, solve: an ApplyPipe handle for this (m, n, b, dtype) and a Solve handle for (n, b, dtype),
+        given together — the apply and the solve then run pipelined over workgroups (tqr_lstsq_pipe),
+        with the same bits."""
         ldda = ldda or A.shape[-1]
         lddb = lddb or B.shape[-1]
         nrhs = B.shape[0] if nrhs is None else nrhs
-        check(lib().tqr_lstsq(self.h, 1 if trans else 0, _ptr(A), ldda, _ptr(B), nrhs, lddb,
-                              None if res is None else _ptr(res), _stream_handle(stream)), "tqr_lstsq")
+        pres = None if res is None else _ptr(res)
+        if pipe is None and solve is None:
+            check(lib().tqr_lstsq(self.h, 1 if trans else 0, _ptr(A), ldda, _ptr(B), nrhs, lddb, pres,
+                                  _stream_handle(stream)), "tqr_lstsq")
+            return
+        if pipe is None or solve is None:
+            raise TQRError("ApplyQ.lstsq: pipe= and solve= go together (tqr_lstsq_pipe takes both)")
+        pipe._match(self, nrhs, "ApplyQ.lstsq")
+        if (solve.n, solve.b, solve.dtype) != (self.n, self.b, self.dtype) or nrhs > solve.nrhs_max:
+            raise TQRError(f"ApplyQ.lstsq: the Solve handle is for n = {solve.n}, b = {solve.b}, dtype {solve.dtype}, "
+                           f"nrhs <= {solve.nrhs_max}, not {self.n}, {self.b}, {self.dtype}, {nrhs}")
+        check(lib().tqr_lstsq_pipe(pipe.h, solve.h, self.h, 1 if trans else 0, _ptr(A), ldda, _ptr(B), nrhs, lddb, pres,
+                                   _stream_handle(stream)), "tqr_lstsq_pipe")
 
     def __del__(self):
         try:
@@ -518,6 +549,63 @@ class ApplyQ:
                 lib().tqr_apply_destroy(self.h)
         except Exception:
             pass
+
+
+class ApplyPipe:
+    """The apply of Q / Q^T pipelined over workgroups (tqr_apply_pipe, include/tqr.h "pipelined
+    apply"): the bits of ApplyQ.apply, on one CU per step of the factorisation and 64 right-hand sides
+    instead of one CU per 64 right-hand sides — the call for a narrow C. Create once per (m, n, b,
+    dtype) and largest nrhs, independent of any ApplyQ; apply() takes a prepared ApplyQ of the same
+    shape. Calls on one handle are serialised on the GPU and need no host synchronisation in between."""
+
+    def __init__(self, m, n, b, dtype, nrhs_max):
+        self.m, self.n, self.b, self.nrhs_max = m, n, b, nrhs_max
+        self.dtype = dtype if isinstance(dtype, int) else _dtype_code(dtype)
+        self.h = None
+        h = _P()
+        check(lib().tqr_apply_pipe_create(ctypes.byref(h), m, n, b, self.dtype, nrhs_max), "tqr_apply_pipe_create")
+        self.h = h
+
+    def workspace_bytes(self):
+        return int(lib().tqr_apply_pipe_workspace_bytes(self.h))
+
+    def _match(self, ap, nrhs, who):
+        if (ap.m, ap.n, ap.b, ap.dtype) != (self.m, self.n, self.b, self.dtype):
+            raise TQRError(f"{who}: the ApplyPipe handle is for (m, n, b, dtype) = {(self.m, self.n, self.b, self.dtype)}, "
+                           f"the ApplyQ for {(ap.m, ap.n, ap.b, ap.dtype)}")
+        if nrhs > self.nrhs_max:
+            raise TQRError(f"{who}: nrhs = {nrhs} exceeds the ApplyPipe handle's nrhs_max = {self.nrhs_max}")
+
+    def apply(self, ap, A, C, trans=True, nrhs=None, ldda=None, lddc=None, stream=None):
+        """C (nrhs, lddc) <- Q^T C (trans) or Q C in place, as ap.apply(A, C, ...): ap a prepared ApplyQ
+        of this handle's shape and dtype, A as given to its prepare(). Stream-ordered."""
+        ldda = ldda or A.shape[-1]
+        lddc = lddc or C.shape[-1]
+        nrhs = C.shape[0] if nrhs is None else nrhs
+        self._match(ap, nrhs, "ApplyPipe.apply")
+        if _dtype_code(C.dtype) != self.dtype or _dtype_code(A.dtype) != self.dtype:
+            raise TQRError("ApplyPipe.apply: A and C must be of the handle's dtype")
+        check(lib().tqr_apply_pipe_q(self.h, ap.h, 1 if trans else 0, _ptr(A), ldda, _ptr(C), nrhs, lddc,
+                                     _stream_handle(stream)), "tqr_apply_pipe_q")
+
+    def status(self, stream=None):
+        """Synchronise `stream` and the handle's last call; raise if a wait timed out (tqr_apply_pipe_status)."""
+        check(lib().tqr_apply_pipe_status(self.h, _stream_handle(stream)), "tqr_apply_pipe_status")
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().tqr_apply_pipe_destroy(self.h)
+        except Exception:
+            pass
+
+
+def apply_pipe_ticket(kmax, nstrips, trans, ticket):
+    """Host-only: (strip, step) of a ticket of the pipelined apply (tqr_apply_pipe_ticket)."""
+    st, step = _I(), _I()
+    check(lib().tqr_apply_pipe_ticket(kmax, nstrips, 1 if trans else 0, ticket, ctypes.byref(st), ctypes.byref(step)),
+          "tqr_apply_pipe_ticket")
+    return st.value, step.value
 
 
 class Solve:

@@ -165,7 +165,8 @@ long tqr_total_tasks(int m, int n, int b);
  *                reflector untransposed), so Q (Q^T C) = C. Q itself is the apply to an identity.
  * fp32 handles load and store float and compute in fp64, as the tile updates of the single-tile API.
  * One workgroup per 64 columns of C walks the whole reflector sequence serially; workgroups never
- * wait for each other (the kernel has no counters or flags), so a narrow C uses few CUs.
+ * wait for each other (the kernel has no counters or flags), so a narrow C uses few CUs — the
+ * "pipelined apply" below (tqr_apply_pipe_q, tqr_lstsq_pipe) computes the same bits on one CU per step.
  * Single-GPU factorisations only: the packed per-rank storage of a tqr_dist_plan is not supported.
  *
  * create validates as tqr_plan_create (before any device call) and allocates the T workspace:
@@ -289,7 +290,8 @@ int tqr_lstsq_fused(tqr_plan* plan, void* dAB, int ldda, void* dtau_compact, int
  * arguments, same results bit for bit. sv must have been created for (steps * b, b, the plan's dtype)
  * with nrhs_max >= nrhs, else TQR_EINVAL (with tqr_lstsq_fused's own argument errors, before any
  * device call). Launch status: tqr_plan_status for the factorisation, tqr_solve_status for the solve.
- * tqr_lstsq has no such variant: its apply strip, not the solve, dominates a narrow call. */
+ * tqr_lstsq's variant is tqr_lstsq_pipe ("pipelined apply" below): its apply strip, not the solve,
+ * dominates a narrow call, so it takes the pipelined apply with this solve. */
 typedef struct tqr_solve tqr_solve;
 int tqr_solve_create(tqr_solve** sv, int n, int b, int dtype, int nrhs_max);
 size_t tqr_solve_workspace_bytes(const tqr_solve* sv);
@@ -300,6 +302,75 @@ void tqr_solve_destroy(tqr_solve* sv);
 int tqr_solve_ticket(int T, int nstrips, int trans, int ticket, int* strip, int* row);
 int tqr_lstsq_fused_solve(tqr_plan* plan, tqr_solve* sv, void* dAB, int ldda, void* dtau_compact, int nrhs,
                           void* dres, void* stream);
+
+/* ---- pipelined apply: tqr_apply_q spread over workgroups, for narrow right-hand sides ----------
+ * tqr_apply_pipe_q computes what tqr_apply_q computes, bit for bit, and its semantics are
+ * tqr_apply_q's word for word: dC <- Q^T dC (TQR_TRANS) or Q dC (TQR_NOTRANS) in place, Q the
+ * orthogonal factor of the factorisation `ap` was last prepared on (dA / ldda as given to
+ * tqr_apply_prepare; dA is not written); rows >= m and columns >= nrhs of C's allocation are not
+ * touched; inf and NaN propagate exactly as there (the same operations on the same operands in the
+ * same order); fp32 storage computes in fp64 and rounds a row tile to float whenever it is stored.
+ * Method: one workgroup per (64-column strip of C, step k of the factorisation) instead of one per
+ * strip. The workgroup of step k runs that step's UNMQR and its TSMQRs down the tile rows (up, for
+ * Q), waiting for each row tile C_l until the step before it has released it, and releases it in
+ * turn through a flag in the handle's workspace — a wavefront over (step, row tile) whose serial
+ * chain is about p + 2 kmax tile operations (p = m / b, kmax = min(m, n) / b) instead of all
+ * kmax p - kmax (kmax - 1) / 2 of them, on up to kmax CUs per strip instead of one.
+ * Measured on an MI355X, fp64, 64 right-hand sides: 15.7 ms against tqr_apply_q's
+ * 416.9 ms at 16384 x 16384, b = 256, and 2.59 against 18.3 ms at 4096 x 4096, b = 128; tqr_lstsq_pipe
+ * 25.0 against tqr_lstsq's 542.9 ms, and 4.11 against 27.6 ms. No crossover was found up to nrhs = n:
+ * at 16384 x 16384 the pipelined call is also the faster one for 1024, 4096 and 16384 columns (23.0,
+ * 73.6 and 282.8 ms against 391.6, 397.5 and 422.7 ms). Beyond nrhs = n nothing was measured;
+ * tqr_apply_q runs two workgroups per CU from 2 x 64 x (CU count) columns on, which this kernel
+ * cannot, so prefer tqr_apply_q there until measured.
+ * Work items are handed out by an atomic ticket in dependency order, so a workgroup only ever waits
+ * for workgroups that are already running, however few fit on the device. Every wait is bounded
+ * (5 s): on expiry the kernel sets the handle's error word and all its workgroups leave — it
+ * cannot hang. tqr_apply_pipe_status synchronises `stream` and the handle's last call and returns
+ * TQR_OK, or TQR_EHIP once after a wait timed out (C is then undefined; the handle stays usable).
+ *
+ * tqr_apply_pipe_create: a handle for m x n factorisations of tile size b and `dtype` (validated as
+ * tqr_apply_create validates them), for up to nrhs_max >= 1 right-hand sides. It is independent of
+ * any apply handle and owns tqr_apply_pipe_workspace_bytes of device memory: the ticket counter and
+ * the error word (128 bytes with their padding) and one 4-byte flag per (strip, stored tile (l, k),
+ * l >= k) — ceil(nrhs_max / 64) * (kmax p - kmax (kmax - 1) / 2) flags. Calls allocate nothing.
+ * tqr_apply_pipe_q takes the pipelined handle and a prepared apply handle of the same (m, n, b,
+ * dtype). Ordering: the call's stream first waits for ap's last prepare, and the call is recorded
+ * among ap's applies, so a later tqr_apply_prepare waits for it — exactly as tqr_apply_q. The calls
+ * of one tqr_apply_pipe are serialised like a tqr_solve's: concurrent host threads are mutually
+ * excluded while they enqueue, and each call's stream first waits for the handle's previous call
+ * (whatever its stream); use one handle per concurrent apply (any number may share one prepared
+ * ap). Consecutive calls need no host synchronisation: flags carry a per-call epoch and the ticket
+ * counter is re-armed in stream order.
+ * Every argument error returns TQR_EINVAL before any device call: create with tqr_apply_create's
+ * errors, nrhs_max < 1, or a shape whose grid of ceil(nrhs_max / 64) * kmax workgroups would pass
+ * 2^31; tqr_apply_pipe_q with a NULL handle, ap or pointer, a bad trans, nrhs < 1 or > nrhs_max,
+ * ldda or lddc below m or beyond the library's leading-dimension bound, an ap made for another
+ * (m, n, b, dtype), or an ap that was never prepared. A missing or non-gfx950 device is reported
+ * after that validation: tqr_apply_pipe_create then still returns a handle (without device
+ * memory), and every call on it returns TQR_ENODEV.
+ *
+ * tqr_apply_pipe_ticket (host only, no GPU): the work item (*strip, *step) of ticket `ticket` on
+ * kmax steps and nstrips strips — the function the kernel itself evaluates. Tickets
+ * 0 .. kmax*nstrips-1 map one to one onto the items, and the one item a step waits for (step - 1
+ * for TQR_TRANS, step + 1 for TQR_NOTRANS, same strip) has a smaller ticket. Anything out of range
+ * returns TQR_EINVAL and writes nothing.
+ *
+ * tqr_lstsq_pipe: tqr_lstsq with tqr_apply_pipe_q in place of tqr_apply_q and tqr_solve_trsm_r in
+ * place of tqr_trsm_r, both directions; same arguments, same results bit for bit (X, the rest of
+ * Q^T B, the zeroed rows of TQR_TRANS, dres). pp must match ap as above; sv must have been created
+ * for (n, b, dtype) with nrhs_max >= nrhs, else TQR_EINVAL (with tqr_lstsq's own argument errors,
+ * before any device call). Launch status: tqr_apply_pipe_status and tqr_solve_status. */
+typedef struct tqr_apply_pipe tqr_apply_pipe;
+int tqr_apply_pipe_create(tqr_apply_pipe** pp, int m, int n, int b, int dtype, int nrhs_max);
+size_t tqr_apply_pipe_workspace_bytes(const tqr_apply_pipe* pp);
+int tqr_apply_pipe_q(tqr_apply_pipe* pp, tqr_apply* ap, int trans, const void* dA, int ldda, void* dC, int nrhs,
+                     int lddc, void* stream);
+int tqr_apply_pipe_status(tqr_apply_pipe* pp, void* stream);
+void tqr_apply_pipe_destroy(tqr_apply_pipe* pp);
+int tqr_apply_pipe_ticket(int kmax, int nstrips, int trans, int ticket, int* strip, int* step);
+int tqr_lstsq_pipe(tqr_apply_pipe* pp, tqr_solve* sv, tqr_apply* ap, int trans, const void* dA, int ldda, void* dB,
+                   int nrhs, int lddb, void* dres, void* stream);
 
 /* ---- multi-GPU: tile-column partition, one process per GPU ---------------------------------
  * Rank r owns the tile columns j with tqr_dist_owner(j) == r — snake order over the ranks

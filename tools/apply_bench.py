@@ -7,7 +7,17 @@ Two yardsticks from the same process:
       traffic at their best — with as many b-column blocks as the apply has TSMQR tile updates (capped
       by the batch's 32-bit device matrix), reported per block;
   (b) torch.geqrf + torch.ormqr (Q^T C) on the same shape, "unavailable" if torch cannot run them here.
-Usage: python tools/apply_bench.py [--reps N] [--no-torch] [m:b ...]"""
+Pipelined apply: --pipe times, per shape and nrhs (--nrhs a,b,...; default 64),
+tqr_apply_q against tqr_apply_pipe_q in both directions and tqr_lstsq against tqr_lstsq_pipe (least
+squares with residual norms, and the minimum-norm direction) in the same run, with all `reps` timings of
+every call (`*_runs_ms`) so the run-to-run spread can be read next to the difference, and the model
+(p + 2 kmax) / (stored tiles) x the tqr_apply_q time of the same run next to the measured time. Nothing
+else is timed in that mode. Crossover measured on an MI355X (fp64, 16384^2, b = 256): none up to nrhs = n —
+the pipelined call is 26.5 x faster at nrhs = 64 (15.7 against 416.9 ms), 17 x at 1024, 5.4 x at 4096 and
+still 1.49 x at 16384 columns (282.8 against 422.7 ms), where tqr_apply_q has exactly one workgroup per CU.
+Beyond nrhs = n it was not measured: tqr_apply_q then runs two workgroups per CU, which the pipelined kernel
+cannot, so a crossover may lie there.
+Usage: python tools/apply_bench.py [--reps N] [--no-torch] [--pipe [--nrhs a,b,...]] [m:b ...]"""
 import ctypes
 import json
 import os
@@ -19,12 +29,19 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import tqr  # noqa: E402
 
 
+PIPE = {"on": False, "nrhs": [64]}  # --pipe / --nrhs (parse is shared with tools/solve_bench.py)
+
+
 def parse(argv):
     reps, use_torch, shapes = 3, True, []
     it = iter(argv)
     for a in it:
         if a == "--reps":
             reps = int(next(it))
+        elif a == "--pipe":
+            PIPE["on"] = True
+        elif a == "--nrhs":
+            PIPE["nrhs"] = [int(v) for v in next(it).split(",")]
         elif a == "--no-torch":
             use_torch = False
         else:
@@ -44,11 +61,12 @@ def apply_flops(m, n, b, nrhs):
     return (4.0 * ts + 2.0 * ge) * b * b * nrhs
 
 
-def timed(fn, reps):
+def timed(fn, reps, warm=True):
     """best device time (ms) of fn() over `reps` runs after one warm-up run"""
     import torch
-    fn()
-    torch.cuda.synchronize()
+    if warm:
+        fn()
+        torch.cuda.synchronize()
     best = None
     for _ in range(reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -59,6 +77,79 @@ def timed(fn, reps):
         ms = e0.elapsed_time(e1)
         best = ms if best is None else min(best, ms)
     return best
+
+
+def timed_all(fn, reps):
+    """device times (ms) of `reps` runs of fn() after one warm-up run, in run order"""
+    import torch
+    fn()
+    torch.cuda.synchronize()
+    return [round(timed(fn, 1, warm=False), 3) for _ in range(reps)]
+
+
+def pipe_records(m, b, nrhs_list, reps):
+    """tqr_apply_q / tqr_apply_pipe_q and tqr_lstsq / tqr_lstsq_pipe on one fp64 m x m factorisation."""
+    import torch
+    n = m
+    cs = torch.cuda.current_stream()
+    A = torch.empty((n, m), dtype=torch.float64, device="cuda")
+    tau = torch.zeros((n // b, m), dtype=torch.float64, device="cuda")
+    tqr.fill_randzo(A, m, n, 5)
+    plan = tqr.TiledQR(m, n, b, torch.float64)
+    plan.execute(A, tau)
+    plan.status()
+    ap = tqr.ApplyQ(m, n, b, torch.float64)
+    ap.prepare(A, tau, stream=cs)
+    p = kmax = m // b
+    tiles = kmax * p - kmax * (kmax - 1) // 2
+    for nrhs in nrhs_list:
+        pp = tqr.ApplyPipe(m, n, b, torch.float64, nrhs)
+        sv = tqr.Solve(n, b, torch.float64, nrhs)
+        C = torch.empty((nrhs, m), dtype=torch.float64, device="cuda")
+        tqr.fill_randzo(C, m, nrhs, 9)
+        # the two calls on the same input, at this size: the same bytes (both directions, one after the other)
+        C1 = C.clone()
+        for trans in (True, False):
+            ap.apply(A, C, trans=trans, stream=cs)
+            ap.apply(A, C1, trans=trans, stream=cs, pipe=pp)
+        pp.status(cs)
+        same = bool(torch.equal(C.view(torch.int64), C1.view(torch.int64)))
+        del C1
+        runs = {}
+        for name, trans, pipe in (("apply_qt", True, None), ("apply_qt_pipe", True, pp),
+                                  ("apply_q", False, None), ("apply_q_pipe", False, pp)):
+            runs[name] = timed_all(lambda: ap.apply(A, C, trans=trans, stream=cs, pipe=pipe), reps)
+        # the solves run in place: every timed least-squares call starts from the same right-hand side
+        X0 = C.clone()
+        tqr.fill_randzo(X0, m, nrhs, 9)
+        res = torch.zeros((nrhs,), dtype=torch.float64, device="cuda")
+        t_copy = timed(lambda: C.copy_(X0), reps)
+
+        def ls(trans, piped):
+            def run():
+                C.copy_(X0)
+                if piped:
+                    ap.lstsq(A, C, trans=trans, res=res, stream=cs, pipe=pp, solve=sv)
+                else:
+                    ap.lstsq(A, C, trans=trans, res=res, stream=cs)
+            return run
+
+        for name, trans, piped in (("lstsq", False, False), ("lstsq_pipe", False, True),
+                                   ("lstsq_t", True, False), ("lstsq_t_pipe", True, True)):
+            runs[name] = [round(t - t_copy, 3) for t in timed_all(ls(trans, piped), reps)]
+        pp.status(cs)
+        sv.status(cs)
+        best = {k: min(v) for k, v in runs.items()}
+        rec = {"record": "pipe", "dtype": "f64", "m": m, "n": n, "b": b, "nrhs": nrhs, "copy_ms": round(t_copy, 3),
+               "stored_tiles": tiles, "path_tiles": p + 2 * kmax, "bytes_equal": same,
+               **{k + "_ms": v for k, v in best.items()},
+               "model_qt_pipe_ms": round(best["apply_qt"] * (p + 2 * kmax) / tiles, 3),
+               "model_q_pipe_ms": round(best["apply_q"] * (p + 2 * kmax) / tiles, 3),
+               **{k + "_runs_ms": v for k, v in runs.items()},
+               "spread_max_ms": round(max(max(v) - min(v) for v in runs.values()), 3)}
+        print(json.dumps(rec), flush=True)
+        del pp, sv, C, X0, res
+        torch.cuda.empty_cache()
 
 
 def dapp_yardstick(b, want, reps):
@@ -102,6 +193,10 @@ def main(argv):
     reps, use_torch, shapes = parse(argv)
     assert torch.cuda.is_available(), "apply_bench.py measures on the GPU only"
     cs = torch.cuda.current_stream()
+    if PIPE["on"]:
+        for m, b in shapes:
+            pipe_records(m, b, PIPE["nrhs"], reps)
+        return
     for m, b in shapes:
         n = m
         A = torch.empty((n, m), dtype=torch.float64, device="cuda")
