@@ -37,6 +37,11 @@
 //   * every spin is bounded (PIPE_TIMEOUT): on expiry the error word is set, the workgroup leaves
 //     without publishing, and every workgroup that sees the word — in a spin or before it takes a
 //     ticket — leaves too. tqr_apply_pipe_status reports it.
+//
+// k_form_q_pipe (tqr_apply_pipe_form_q) is the Q direction of the same on the first ncols columns of an
+// identity that is never stored: only the (strip, step) items that meet non-zero data exist
+// (form_q_ticket_map), and a row tile's first operation takes the 0 / 1 pattern from registers. Same
+// flags, hand-over, bounded waits and handle.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -60,6 +65,42 @@ __host__ __device__ inline void apply_ticket_map(int kmax, int nstrips, bool tra
   const int pos = t / nstrips;
   *strip = t - pos * nstrips;
   *step = trans ? pos : kmax - 1 - pos;
+}
+
+// ---------------------------------------------------------------------------------------
+// Form Q (tqr_apply_pipe_form_q): Q applied to E = the first ncols columns of I_m, without the work on
+// E's zero blocks. Strip s of E (columns 64 s .. min(64 s + 63, ncols - 1)) is non-zero in the row tiles
+// jlo(s) .. jhi(s) only, and step k of Q touches the row tiles >= k: the steps k > jhi(s) would turn
+// zeros into zeros and are no items. The items are (s, k) with k <= kf(s) = min(jhi(s), kmax - 1) —
+// step k has the strips s >= smin(k) = floor(k b / 64), and exists if k b <= ncols - 1.
+// ---------------------------------------------------------------------------------------
+// steps that have items: k = 0 .. form_q_steps - 1
+__host__ __device__ inline int form_q_steps(int kmax, int b, int ncols) {
+  const int ka = (ncols - 1) / b + 1;
+  return ka < kmax ? ka : kmax;
+}
+// Work item of ticket t: tickets go step-descending as apply_ticket_map's for Q, over the active
+// strips of each step only — so the one producer of (strip, step), which is (strip, step + 1) where step
+// < kf(strip), has a smaller ticket. False: t is no ticket (t >= the item count). The search walks at
+// most kmax counts, once per workgroup, in scalar registers that are free again before the tile loops.
+__host__ __device__ inline bool form_q_ticket_map(int kmax, int b, int ncols, int t, int* strip, int* step) {
+  const int nstrips = (ncols + 63) >> 6;
+  for (int k = form_q_steps(kmax, b, ncols) - 1; k >= 0; --k) {
+    const int smin = (k * b) >> 6, cnt = nstrips - smin;  // (k b <= ncols - 1: no overflow, cnt >= 1)
+    if (t < cnt) {
+      *strip = smin + t;
+      *step = k;
+      return true;
+    }
+    t -= cnt;
+  }
+  return false;
+}
+static inline long long form_q_items(int kmax, int b, int ncols) {
+  const int nstrips = (ncols + 63) >> 6;
+  long long n = 0;
+  for (int k = form_q_steps(kmax, b, ncols) - 1; k >= 0; --k) n += nstrips - ((k * b) >> 6);
+  return n;
 }
 
 struct ApplyPipeArgs {
@@ -209,6 +250,171 @@ __global__ __launch_bounds__(NT) void k_apply_q_pipe(ApplyPipeArgs pa) {
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Form Q: k_apply_q_pipe<B, S, false> on form_q_ticket_map's items, with C = Q output-only (a.nrhs is
+// ncols). Same thread layout, resources, flags, wait and publish, the same unmqr / tsmqr on the same
+// operands; what differs is where a row tile's values come from the first time the call touches it:
+// E's 0 / 1 pattern built in registers (synth_rows) instead of load_rows. That is C_k in every step —
+// no step above k touches row tile k — and every C_l in the strip's first step kf, which therefore
+// waits for nothing. A sibling kernel, not a template flag: k_apply_q_pipe's text and code stay as
+// they were.
+// ---------------------------------------------------------------------------------------
+// stage_vq<B, S, false, true> (a TSMQR tile's V group, columns reversed: the same image) with the batch
+// written out: up to eight loads issued, then their LDS writes, a scheduling barrier in between. In
+// k_form_q_pipe<256, .> the compiler had turned stage_vq's unrolled loop into load - wait - write per
+// element (256 exposed load latencies per tile operation, 1.5 x its time); k_apply_q_pipe gets the
+// batch from the same loop by itself, and stage_vq stays as it is for it.
+template <int B, typename S>
+__device__ __forceinline__ void stage_vq_ts_rev(double* Vs, const S* __restrict__ vt, size_t ldm, int c0) {
+  using g = Geo<B>;
+  constexpr int N = B * g::IB / NT, U = N < 8 ? N : 8;  // elements per thread, per batch
+  static_assert(B * g::IB % NT == 0 && N % U == 0, "whole batches");
+  const __amdgpu_buffer_rsrc_t rs = uniform_rsrc(vt + (size_t)c0 * ldm);
+  for (int i0 = 0; i0 < N; i0 += U) {
+    double v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int idx = threadIdx.x + (i0 + u) * NT, r = idx % B, c = idx / B;
+      const unsigned off = (unsigned)(((size_t)c * ldm + r) * sizeof(S));
+      if constexpr (sizeof(S) == 8) {
+        const auto w = __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0);
+        v[u] = dbl_of(w[0], w[1]);
+      } else {
+        v[u] = (double)__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int idx = threadIdx.x + (i0 + u) * NT, r = idx % B, c = idx / B;
+      Vs[r * g::VP + g::pc(g::IB - 1 - c)] = v[u];
+    }
+  }
+}
+
+template <int B, typename S>
+__global__ __launch_bounds__(NT) void k_form_q_pipe(ApplyPipeArgs pa) {
+  using G = Geo<B>;
+  constexpr int IB = G::IB, NG = G::NG;
+  constexpr int SC1 = 16;  // aux bits of every C access
+  extern __shared__ __align__(16) double lds[];
+  double* Vs = lds;
+  double* Ts = Vs + G::VSZ;
+  __shared__ int s_tk, s_ok;
+  const ApplyArgs& a = pa.q;
+
+  if (threadIdx.x == 0)
+    s_tk = ld_sc1(pa.ws + PIPE_ERR) ? -1 : __hip_atomic_fetch_add((pint*)(pa.ws + PIPE_TICKET), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  const int tk = __builtin_amdgcn_readfirstlane(s_tk);
+  int strip, k;
+  if (tk < 0 || !form_q_ticket_map(a.kmax, B, a.nrhs, tk, &strip, &k)) return;  // (tk < 0: k_apply_q_pipe)
+  // the strip's first step kf = min(jhi, kmax - 1), jhi the row tile of its last column
+  const int lastcol = strip * 64 + 63 < a.nrhs - 1 ? strip * 64 + 63 : a.nrhs - 1;
+  const bool first = k == (lastcol / B < a.kmax - 1 ? lastcol / B : a.kmax - 1);
+
+  // (k_apply_q_pipe's values, parked in VGPRs for its reasons)
+  const size_t ldc = a.ldc;
+  const int lane = threadIdx.x & 63, x = lane >> 4, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int col0 = strip * 64 + 16 * w, col = col0 + (lane & 15);
+  const bool active = col0 < a.nrhs;  // wave-uniform
+  int on = col < a.nrhs;
+  unsigned long long flv = (unsigned long long)(pa.ws + PIPE_HDR) + (unsigned long long)strip * (unsigned long long)pa.nslot * sizeof(int);
+  unsigned long long errv = (unsigned long long)(pa.ws + PIPE_ERR);
+  int epoch = pa.epoch, nact = a.nrhs - col0;
+  asm volatile("" : "+v"(on), "+v"(flv), "+v"(errv), "+v"(epoch), "+v"(nact));
+  unsigned long long akv = (unsigned long long)((const S*)a.A + (size_t)k * B * (size_t)a.lda), ldav = (unsigned long long)a.lda;
+  unsigned long long twv = (unsigned long long)a.Tw;
+  asm volatile("" : "+v"(akv), "+v"(ldav), "+v"(twv));
+  const S* const Ak = (const S*)akv;
+  const size_t lda = ldav;
+  ApplyArgs at = a;  // (tg_ptr reads Tw and p)
+  at.Tw = (double*)twv;
+  S* Cw = (S*)a.C + (size_t)(active ? col0 : 0) * ldc;
+  const __amdgpu_buffer_rsrc_t rc = uniform_rsrc(Cw);
+  const unsigned coff = head_off<B, S>(ldc, 0);
+  const unsigned koff = coff + (unsigned)k * (unsigned)(B * sizeof(S));
+  double X[G::NKS];
+  double H[G::NRI];
+
+  // flags as in k_apply_q_pipe: fmine[l] is (k, l), fprod[l] is (k + 1, l) (never used in step kf)
+  unsigned long long fmine = flv + (unsigned long long)((long long)tile_slot(k, k, a.p) - k) * sizeof(int);
+  unsigned long long fprod = flv + (unsigned long long)((long long)tile_slot(k + 1, k + 1, a.p) - (k + 1)) * sizeof(int);
+  asm volatile("" : "+v"(fmine), "+v"(fprod));
+  auto wait = [&](int l) {
+    if (threadIdx.x == 0) s_ok = pipe_spin_ge((int*)fprod + l, epoch, (int*)errv) ? 1 : 0;
+    __syncthreads();
+    return s_ok != 0;
+  };
+  auto publish = [&](int l) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store((pint*)((int*)fmine + l), epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  // E's values in the lane's rows of row tile l: 1.0 where the global row equals the global column,
+  // +0.0 elsewhere and in a masked lane (load_rows' zeros)
+  auto synth_rows = [&](int l) {
+    const int d = on != 0 ? col - (l * B + x) : -1;  // 4 x the lane's k-step that holds the diagonal
+#pragma unroll
+    for (int ks = 0; ks < G::NKS; ++ks) X[ks] = d == 4 * ks ? 1.0 : 0.0;
+  };
+  // k_apply_q_pipe's unmqr(k) for Q
+  auto unmqr = [&](const bool active) {
+    const S* Vt = Ak + (size_t)k * B;
+    if (active) load_rows<B, S, SC1>(X, rc, koff, on != 0);
+    for (int gi = 0; gi < NG; ++gi) {
+      const int g = NG - 1 - gi;
+      __syncthreads();
+      stage_vq<B, S, true, true>(Vs, Vt, lda, g * IB);
+      stage_tq<B, true>(Ts, tg_ptr<B>(at, k, k, g));
+      __syncthreads();
+      if (active) apply_group<B, false>(Vs, Ts, X, H, g * IB / 4);
+    }
+    if (active) store_rows<B, S, SC1>(X, rc, koff, on != 0);
+  };
+  // k_apply_q_pipe's tsmqr(l, k) for Q, C_l synthesised in step kf
+  auto tsmqr = [&](int l) {
+    const S* Vt = Ak + (size_t)l * B;
+    const unsigned loff = coff + (unsigned)l * (unsigned)(B * sizeof(S));
+    if (active) {
+      if (first) synth_rows(l);
+      else load_rows<B, S, SC1>(X, rc, loff, on != 0);
+    }
+    for (int gi = 0; gi < NG; ++gi) {
+      const int g = NG - 1 - gi;
+      __syncthreads();
+      stage_vq_ts_rev<B, S>(Vs, Vt, lda, g * IB);
+      stage_tq<B, true>(Ts, tg_ptr<B>(at, l, k, g));
+      __syncthreads();
+      if (active) {
+        const unsigned hoff = koff + (unsigned)((g * IB + 3 - 2 * x) * (int)sizeof(S));
+        load_hrows<B, S, true, SC1>(H, rc, hoff, on != 0);
+        apply_group<B, true>(Vs, Ts, X, H, 0);
+        store_hrows<B, S, true, SC1>(H, rc, hoff, on != 0);
+      }
+    }
+    if (active) store_rows<B, S, SC1>(X, rc, loff, on != 0);
+  };
+
+  // C_k goes to memory ahead of everything: tsmqr takes its head rows from there group by group (other
+  // lanes' rows of the wave's own columns), unmqr all of it. No byte of C is read that this call has
+  // not stored: C_k here, every C_l by this step (kf) or behind the producer's flag.
+  if (active) {
+    synth_rows(k);
+    store_rows<B, S, SC1>(X, rc, koff, on != 0);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  for (int l = a.p - 1; l > k; --l) {
+    if (!first && !wait(l)) return;  // (l = k+1: flag (k+1, k+1), the producer's UNMQR)
+    tsmqr(l);
+    publish(l);
+  }
+  asm volatile("" : "+v"(nact));  // (`active` anew, as in k_apply_q_pipe)
+  unmqr(__builtin_amdgcn_readfirstlane(nact) > 0);
+  publish(k);
+}
+
 typedef void (*apfn)(ApplyPipeArgs);
 template <int B>
 static apfn apipe_kernel(int dtype, int trans) {
@@ -222,6 +428,19 @@ static apfn apipe_kernel_b(int b, int dtype, int trans) {
     case 64: return apipe_kernel<64>(dtype, trans);
     case 128: return apipe_kernel<128>(dtype, trans);
     default: return apipe_kernel<256>(dtype, trans);
+  }
+}
+template <int B>
+static apfn aform_kernel(int dtype) {
+  return dtype == TQR_F64 ? k_form_q_pipe<B, double> : k_form_q_pipe<B, float>;
+}
+static apfn aform_kernel_b(int b, int dtype) {
+  switch (b) {
+    case 16: return aform_kernel<16>(dtype);
+    case 32: return aform_kernel<32>(dtype);
+    case 64: return aform_kernel<64>(dtype);
+    case 128: return aform_kernel<128>(dtype);
+    default: return aform_kernel<256>(dtype);
   }
 }
 
@@ -242,7 +461,7 @@ struct tqr_apply_pipe {
   int m, n, b, p, kmax, dtype, nrhs_max;
   size_t es, ws_bytes;
   long long nslot;  // flags per strip
-  apfn kn = nullptr, kt = nullptr;
+  apfn kn = nullptr, kt = nullptr, kf = nullptr;  // Q, Q^T, form-Q
   std::mutex mu;        // the enqueue sequence of a call (epoch, event bookkeeping)
   int* d_ws = nullptr;  // device workspace (null until a gfx950 was seen)
   hipEvent_t evDone = nullptr;
@@ -265,6 +484,7 @@ static int apply_pipe_ready(tqr_apply_pipe* pp) {
   }
   HIPCHK(hipFuncSetAttribute((const void*)pp->kn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS));
   HIPCHK(hipFuncSetAttribute((const void*)pp->kt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS));
+  HIPCHK(hipFuncSetAttribute((const void*)pp->kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS));
   if (!pp->evDone) HIPCHK(hipEventCreateWithFlags(&pp->evDone, hipEventDisableTiming));
   int* ws = nullptr;
   if (hipMalloc(&ws, pp->ws_bytes) != hipSuccess) {
@@ -285,6 +505,41 @@ static bool apply_pipe_args_ok(const tqr_apply_pipe* pp, const tqr_apply* ap, in
   return pp && ap && dA && dC && (trans == TQR_NOTRANS || trans == TQR_TRANS) && nrhs >= 1 && nrhs <= pp->nrhs_max &&
          ldda >= pp->m && lddc >= pp->m && apply_valid_ld(ldda, pp->es) && apply_valid_ld(lddc, pp->es) && ap->m == pp->m &&
          ap->n == pp->n && ap->b == pp->b && ap->dtype == pp->dtype;
+}
+
+// One call of the handle, arguments valid: `kern` on `grid` workgroups, one per work item, ordered
+// against ap's prepares and the handle's previous call (tqr_apply_pipe_q, tqr_apply_pipe_form_q)
+static int apply_pipe_enqueue(tqr_apply_pipe* pp, tqr_apply* ap, apfn kern, unsigned grid, const void* dA, int ldda, void* dC,
+                              int nrhs, int lddc, void* stream) {
+  hipStream_t cs = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lp(pp->mu);  // (always pp's before ap's)
+  std::lock_guard<std::mutex> la(ap->mu);
+  if (!ap->prepared) return TQR_EINVAL;
+  if (const int st = apply_pipe_ready(pp)) return st;
+  HIPCHK(hipStreamWaitEvent(cs, pp->evDone, 0));  // the previous call of this handle (any stream)
+  if (pp->epoch == INT_MAX) {  // the epochs start over: behind the previous call, ahead of this one
+    HIPCHK(hipMemsetAsync(pp->d_ws + PIPE_HDR, 0, pp->ws_bytes - PIPE_HDR * sizeof(int), cs));
+    pp->epoch = 0;
+  }
+  int slot = 0;
+  HIPCHK(apply_enqueue_begin(ap, cs, &slot));
+  ApplyPipeArgs a;
+  a.q.A = dA; a.q.tau = nullptr; a.q.C = dC; a.q.Tw = ap->d_T; a.q.lda = ldda; a.q.ldc = lddc;
+  a.q.m = pp->m; a.q.p = pp->p; a.q.kmax = pp->kmax; a.q.nrhs = nrhs;
+  a.nslot = pp->nslot;
+  a.epoch = pp->epoch + 1;
+  a.ws = pp->d_ws;
+  HIPCHK(hipMemsetAsync(pp->d_ws + PIPE_TICKET, 0, sizeof(int), cs));  // (the error word stays: tqr_apply_pipe_status)
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), PIPE_LDS, cs, a);
+  const hipError_t le = hipGetLastError();
+  // recorded behind whatever was enqueued, so the next call and the next prepare stay ordered after it
+  const hipError_t re = hipEventRecord(pp->evDone, cs);
+  const hipError_t ae = apply_enqueue_end(ap, cs, slot);
+  HIPCHK(le);
+  pp->epoch = a.epoch;  // committed once the launch is enqueued
+  HIPCHK(re);
+  HIPCHK(ae);
+  return TQR_OK;
 }
 
 extern "C" {
@@ -324,6 +579,7 @@ int tqr_apply_pipe_create(tqr_apply_pipe** out, int m, int n, int b, int dtype, 
   pp->ws_bytes = ((size_t)PIPE_HDR + nstrips * (size_t)pp->nslot) * sizeof(int);
   pp->kn = apipe_kernel_b(b, dtype, TQR_NOTRANS);
   pp->kt = apipe_kernel_b(b, dtype, TQR_TRANS);
+  pp->kf = aform_kernel_b(b, dtype);
   // without a gfx950 the handle exists but holds no device memory: every call on it validates its
   // arguments and then returns TQR_ENODEV
   const int st = apply_pipe_ready(pp);
@@ -340,38 +596,31 @@ size_t tqr_apply_pipe_workspace_bytes(const tqr_apply_pipe* pp) { return pp ? pp
 int tqr_apply_pipe_q(tqr_apply_pipe* pp, tqr_apply* ap, int trans, const void* dA, int ldda, void* dC, int nrhs,
                      int lddc, void* stream) {
   if (!apply_pipe_args_ok(pp, ap, trans, dA, ldda, dC, nrhs, lddc)) return TQR_EINVAL;
-  hipStream_t cs = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lp(pp->mu);  // (always pp's before ap's)
-  std::lock_guard<std::mutex> la(ap->mu);
-  if (!ap->prepared) return TQR_EINVAL;
-  if (const int st = apply_pipe_ready(pp)) return st;
-  HIPCHK(hipStreamWaitEvent(cs, pp->evDone, 0));  // the previous call of this handle (any stream)
-  if (pp->epoch == INT_MAX) {  // the epochs start over: behind the previous call, ahead of this one
-    HIPCHK(hipMemsetAsync(pp->d_ws + PIPE_HDR, 0, pp->ws_bytes - PIPE_HDR * sizeof(int), cs));
-    pp->epoch = 0;
-  }
-  int slot = 0;
-  HIPCHK(apply_enqueue_begin(ap, cs, &slot));
-  ApplyPipeArgs a;
-  a.q.A = dA; a.q.tau = nullptr; a.q.C = dC; a.q.Tw = ap->d_T; a.q.lda = ldda; a.q.ldc = lddc;
-  a.q.m = pp->m; a.q.p = pp->p; a.q.kmax = pp->kmax; a.q.nrhs = nrhs;
-  a.nslot = pp->nslot;
-  a.epoch = pp->epoch + 1;
-  a.ws = pp->d_ws;
-  const unsigned grid = (unsigned)((nrhs + 63) / 64) * (unsigned)pp->kmax;
-  HIPCHK(hipMemsetAsync(pp->d_ws + PIPE_TICKET, 0, sizeof(int), cs));  // (the error word stays: tqr_apply_pipe_status)
-  hipLaunchKernelGGL(trans == TQR_TRANS ? pp->kt : pp->kn, dim3(grid), dim3(NT), PIPE_LDS, cs, a);
-  const hipError_t le = hipGetLastError();
-  // recorded behind whatever was enqueued, so the next call and the next prepare stay ordered after it
-  const hipError_t re = hipEventRecord(pp->evDone, cs);
-  const hipError_t ae = apply_enqueue_end(ap, cs, slot);
-  HIPCHK(le);
-  pp->epoch = a.epoch;  // committed once the launch is enqueued
-  HIPCHK(re);
-  HIPCHK(ae);
-  return TQR_OK;
+  return apply_pipe_enqueue(pp, ap, trans == TQR_TRANS ? pp->kt : pp->kn, (unsigned)((nrhs + 63) / 64) * (unsigned)pp->kmax, dA,
+                            ldda, dC, nrhs, lddc, stream);
 }
 
+int tqr_apply_pipe_form_q(tqr_apply_pipe* pp, tqr_apply* ap, const void* dA, int ldda, void* dQ, int ncols, int lddq,
+                          void* stream) {
+  if (!pp || ncols > pp->m || !apply_pipe_args_ok(pp, ap, TQR_NOTRANS, dA, ldda, dQ, ncols, lddq)) return TQR_EINVAL;
+  // (at most the grid tqr_apply_pipe_create checked)
+  return apply_pipe_enqueue(pp, ap, pp->kf, (unsigned)form_q_items(pp->kmax, pp->b, ncols), dA, ldda, dQ, ncols, lddq, stream);
+}
+
+int tqr_apply_pipe_form_q_items(int kmax, int b, int ncols) {
+  if (kmax < 1 || !apply_valid_b(b) || ncols < 1) return TQR_EINVAL;
+  const long long n = form_q_items(kmax, b, ncols);
+  return n > 0x7fffffffll ? TQR_EINVAL : (int)n;
+}
+
+int tqr_apply_pipe_form_q_ticket(int kmax, int b, int ncols, int ticket, int* strip, int* step) {
+  if (kmax < 1 || !apply_valid_b(b) || ncols < 1 || !strip || !step || ticket < 0) return TQR_EINVAL;
+  int s, k;
+  if (!form_q_ticket_map(kmax, b, ncols, ticket, &s, &k)) return TQR_EINVAL;
+  *strip = s;
+  *step = k;
+  return TQR_OK;
+}
 int tqr_apply_pipe_status(tqr_apply_pipe* pp, void* stream) {
   if (!pp) return TQR_EINVAL;
   std::lock_guard<std::mutex> lk(pp->mu);

@@ -137,6 +137,12 @@ def lib():
     L.tqr_apply_pipe_destroy.restype = None
     L.tqr_apply_pipe_ticket.argtypes = [_I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]
     L.tqr_apply_pipe_ticket.restype = _I
+    L.tqr_apply_pipe_form_q.argtypes = [_P, _P, _P, _I, _P, _I, _I, _P]
+    L.tqr_apply_pipe_form_q.restype = _I
+    L.tqr_apply_pipe_form_q_items.argtypes = [_I, _I, _I]
+    L.tqr_apply_pipe_form_q_items.restype = _I
+    L.tqr_apply_pipe_form_q_ticket.argtypes = [_I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I)]
+    L.tqr_apply_pipe_form_q_ticket.restype = _I
     L.tqr_lstsq_pipe.argtypes = [_P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P]
     L.tqr_lstsq_pipe.restype = _I
     _lib = L
@@ -588,6 +594,23 @@ class ApplyPipe:
         check(lib().tqr_apply_pipe_q(self.h, ap.h, 1 if trans else 0, _ptr(A), ldda, _ptr(C), nrhs, lddc,
                                      _stream_handle(stream)), "tqr_apply_pipe_q")
 
+    def form_q(self, ap, A, Q, ncols=None, ldda=None, lddq=None, stream=None):
+        """Q (ncols, lddq) <- the first ncols columns of the m x m orthogonal factor (row j = column j of
+        Q), 1 <= ncols <= min(m, nrhs_max): ap a prepared ApplyQ of this handle's shape and dtype, A as
+        given to its prepare(). Q is output-only — what it holds on entry does not matter — and the
+        work on the identity's zero blocks is not done (tqr_apply_pipe_form_q). ncols and lddq default
+        to Q's shape. Stream-ordered."""
+        ldda = ldda or A.shape[-1]
+        lddq = lddq or Q.shape[-1]
+        ncols = Q.shape[0] if ncols is None else ncols
+        self._match(ap, ncols, "ApplyPipe.form_q")
+        if ncols > self.m:
+            raise TQRError(f"ApplyPipe.form_q: ncols = {ncols} exceeds m = {self.m}")
+        if _dtype_code(Q.dtype) != self.dtype or _dtype_code(A.dtype) != self.dtype:
+            raise TQRError("ApplyPipe.form_q: A and Q must be of the handle's dtype")
+        check(lib().tqr_apply_pipe_form_q(self.h, ap.h, _ptr(A), ldda, _ptr(Q), ncols, lddq, _stream_handle(stream)),
+              "tqr_apply_pipe_form_q")
+
     def status(self, stream=None):
         """Synchronise `stream` and the handle's last call; raise if a wait timed out (tqr_apply_pipe_status)."""
         check(lib().tqr_apply_pipe_status(self.h, _stream_handle(stream)), "tqr_apply_pipe_status")
@@ -605,6 +628,22 @@ def apply_pipe_ticket(kmax, nstrips, trans, ticket):
     st, step = _I(), _I()
     check(lib().tqr_apply_pipe_ticket(kmax, nstrips, 1 if trans else 0, ticket, ctypes.byref(st), ctypes.byref(step)),
           "tqr_apply_pipe_ticket")
+    return st.value, step.value
+
+
+def apply_pipe_form_q_items(kmax, b, ncols):
+    """Host-only: the number of work items (the grid) of ApplyPipe.form_q (tqr_apply_pipe_form_q_items)."""
+    n = lib().tqr_apply_pipe_form_q_items(kmax, b, ncols)
+    if n < 0:
+        check(n, "tqr_apply_pipe_form_q_items")
+    return n
+
+
+def apply_pipe_form_q_ticket(kmax, b, ncols, ticket):
+    """Host-only: (strip, step) of a ticket of ApplyPipe.form_q (tqr_apply_pipe_form_q_ticket)."""
+    st, step = _I(), _I()
+    check(lib().tqr_apply_pipe_form_q_ticket(kmax, b, ncols, ticket, ctypes.byref(st), ctypes.byref(step)),
+          "tqr_apply_pipe_form_q_ticket")
     return st.value, step.value
 
 
@@ -748,6 +787,29 @@ def form_qt(A, b):
     plan.execute(AI, tau, stream=cs.cuda_stream)
     plan.status(cs.cuda_stream)
     return AI[n:], AI[:n], tau
+
+
+def form_q(F, tau, b, ncols=None):
+    """The first ncols columns of Q (m x m) from a finished factorisation: F (n, m) and tau (kmax, m)
+    as TiledQR.execute left them (any m, n). ncols defaults to min(m, n), the thin Q; up to m gives
+    the full Q. Returns a new (ncols, m) tensor, row j = column j of Q. Prepares an ApplyQ and runs
+    ApplyPipe.form_q — the pipelined apply to an identity that is never stored and whose zero blocks
+    cost nothing (unlike form_qt it needs no unfactorised A and no second factorisation)."""
+    import torch
+    n, m = F.shape
+    ncols = min(m, n) if ncols is None else ncols
+    if ncols < 1 or ncols > m:
+        raise TQRError(f"form_q: ncols = {ncols} must be in 1 .. m = {m}")
+    if tau.dtype != F.dtype:
+        raise TQRError("form_q: F and tau must be of one dtype")
+    ap = ApplyQ(m, n, b, F.dtype)
+    pipe = ApplyPipe(m, n, b, F.dtype, ncols)
+    Q = torch.empty((ncols, m), dtype=F.dtype, device=F.device)
+    cs = torch.cuda.current_stream()
+    ap.prepare(F, tau, stream=cs)
+    pipe.form_q(ap, F, Q, stream=cs)
+    pipe.status(cs)
+    return Q
 
 
 def apply_q_host(F, T, C, b, trans=True):

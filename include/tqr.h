@@ -356,6 +356,44 @@ int tqr_lstsq_fused_solve(tqr_plan* plan, tqr_solve* sv, void* dAB, int ldda, vo
  * for TQR_TRANS, step + 1 for TQR_NOTRANS, same strip) has a smaller ticket. Anything out of range
  * returns TQR_EINVAL and writes nothing.
  *
+ * tqr_apply_pipe_form_q: Q itself. Writes Q[:, 0:ncols], 1 <= ncols <= min(m, nrhs_max), Q the m x m
+ * orthogonal factor of the factorisation `ap` was last prepared on, into dQ (m x ncols, column-major,
+ * lddq >= m, the handle's dtype): ncols = min(m, n) is the thin Q, ncols = m the full one. Rows >= m
+ * and columns >= ncols of the allocation are not touched. dQ is output-only: no byte of it is read
+ * before this call has written it, so what it holds on entry does not matter, inf and NaN included —
+ * no identity is allocated, filled or loaded. The call is tqr_apply_pipe_q(TQR_NOTRANS) on E = the
+ * first ncols columns of I_m without the work on E's zero blocks: the 64-column strip s of E is zero
+ * below row tile jhi(s) (the tile of its last column), and step k of Q touches only row tiles >= k, so
+ * the steps k > jhi(s) of that strip would turn zeros into zeros and are never issued; a row tile's
+ * first operation takes E's 0 / 1 pattern from registers. In tile operations nstrips * sum_k (p - k)
+ * becomes sum_k (p - k) * #{strips with jhi(s) >= k}: 0.67 of them for a square thin Q, towards 0.5 for
+ * a tall one.
+ * Which parts of dA are read (the mirror of tqr_apply_q's rule that R is never read as a value): tile
+ * (l, k) of dA and its T images are read only if k * b <= ncols - 1. With all of V and T finite, dQ is
+ * equal as values to tqr_apply_pipe_q(TQR_NOTRANS) on a dQ pre-filled with E — the same operations in
+ * the same order on the non-zero data; a skipped operation would have produced zeros. The sign of a
+ * zero is left free by this contract (on an MI355X the bytes came out equal in every case tested,
+ * DESIGN.md §17). With inf or NaN in a tile this call does not read the two differ: the apply to E
+ * spreads them, this call never sees them.
+ * Everything else is tqr_apply_pipe_q's, word for word: the same handle and no further workspace (the
+ * flags of tqr_apply_pipe_create cover every (strip, tile) used), the same ordering against ap's
+ * prepare and the handle's previous call, the same epochs, bounded waits and tqr_apply_pipe_status;
+ * TQR_EINVAL before any device call for every argument error — tqr_apply_pipe_q's, and ncols < 1,
+ * ncols > m or ncols > nrhs_max; TQR_ENODEV after validation without a gfx950.
+ * Measured on an MI355X, fp64, thin Q (tools/apply_bench.py --formq), against the fill
+ * of an identity plus tqr_apply_pipe_q on it, and against tqr_apply_q on it: 16384 x 16384, b = 256:
+ * 196.2 ms against 0.3 + 282.6 ms and 423.6 ms (0.67 of the tile operations); 4096 x 4096, b = 128:
+ * 4.71 ms against 0.03 + 6.17 ms and 18.90 ms (0.68); 65536 x 16384, b = 256: 1060.1 ms against
+ * 1.3 + 2092.0 ms and 3030.1 ms (0.53). The call also saves the m x ncols identity itself.
+ * tqr_apply_pipe_form_q_items (host only): the number of work items, which is the grid —
+ * sum over the steps k < kmax with k * b <= ncols - 1 of ceil(ncols / 64) - floor(k * b / 64).
+ * tqr_apply_pipe_form_q_ticket (host only): the work item (*strip, *step) of ticket `ticket` — the
+ * function the kernel itself evaluates. Tickets run step-descending, over a step's strips s >=
+ * floor(step * b / 64) only; they map one to one onto the items, and the one item a step waits for
+ * (step + 1 of the same strip, unless the step is the strip's first) has a smaller ticket. For both,
+ * anything out of range (kmax < 1, b outside {16, 32, 64, 128, 256}, ncols < 1, a ticket outside
+ * 0 .. items-1, a NULL output) returns TQR_EINVAL and writes nothing.
+ *
  * tqr_lstsq_pipe: tqr_lstsq with tqr_apply_pipe_q in place of tqr_apply_q and tqr_solve_trsm_r in
  * place of tqr_trsm_r, both directions; same arguments, same results bit for bit (X, the rest of
  * Q^T B, the zeroed rows of TQR_TRANS, dres). pp must match ap as above; sv must have been created
@@ -369,6 +407,10 @@ int tqr_apply_pipe_q(tqr_apply_pipe* pp, tqr_apply* ap, int trans, const void* d
 int tqr_apply_pipe_status(tqr_apply_pipe* pp, void* stream);
 void tqr_apply_pipe_destroy(tqr_apply_pipe* pp);
 int tqr_apply_pipe_ticket(int kmax, int nstrips, int trans, int ticket, int* strip, int* step);
+int tqr_apply_pipe_form_q(tqr_apply_pipe* pp, tqr_apply* ap, const void* dA, int ldda, void* dQ, int ncols, int lddq,
+                          void* stream);
+int tqr_apply_pipe_form_q_items(int kmax, int b, int ncols);
+int tqr_apply_pipe_form_q_ticket(int kmax, int b, int ncols, int ticket, int* strip, int* step);
 int tqr_lstsq_pipe(tqr_apply_pipe* pp, tqr_solve* sv, tqr_apply* ap, int trans, const void* dA, int ldda, void* dB,
                    int nrhs, int lddb, void* dres, void* stream);
 

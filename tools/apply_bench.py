@@ -17,7 +17,12 @@ the pipelined call is 26.5 x faster at nrhs = 64 (15.7 against 416.9 ms), 17 x a
 still 1.49 x at 16384 columns (282.8 against 422.7 ms), where tqr_apply_q has exactly one workgroup per CU.
 Beyond nrhs = n it was not measured: tqr_apply_q then runs two workgroups per CU, which the pipelined kernel
 cannot, so a crossover may lie there.
-Usage: python tools/apply_bench.py [--reps N] [--no-torch] [--pipe [--nrhs a,b,...]] [m:b ...]"""
+Form Q: --formq times, per shape with ncols = min(m, n), tqr_apply_pipe_form_q against what it
+replaces — the fill of an explicit m x ncols identity, tqr_apply_pipe_q(NOTRANS) on it and tqr_apply_q on it —
+alternating the calls run by run, with all timings (`*_runs_ms`), the tile-operation counts of both item sets,
+and whether the two results have the same values and the same bytes at this size. A shape "m:b:n" is a tall
+m x n factorisation (--formq only). Nothing else is timed in that mode.
+Usage: python tools/apply_bench.py [--reps N] [--no-torch] [--pipe [--nrhs a,b,...]] [--formq] [m:b ...]"""
 import ctypes
 import json
 import os
@@ -30,6 +35,7 @@ import tqr  # noqa: E402
 
 
 PIPE = {"on": False, "nrhs": [64]}  # --pipe / --nrhs (parse is shared with tools/solve_bench.py)
+FORMQ = {"on": False, "n": {}}  # --formq; n of the shapes given as m:b:n
 
 
 def parse(argv):
@@ -42,11 +48,15 @@ def parse(argv):
             PIPE["on"] = True
         elif a == "--nrhs":
             PIPE["nrhs"] = [int(v) for v in next(it).split(",")]
+        elif a == "--formq":
+            FORMQ["on"] = True
         elif a == "--no-torch":
             use_torch = False
         else:
-            m, b = a.split(":")
+            m, b, *n = a.split(":")
             shapes.append((int(m), int(b)))
+            if n:
+                FORMQ["n"][shapes[-1]] = int(n[0])
     return reps, use_torch, shapes or [(4096, 128), (16384, 256)]
 
 
@@ -152,6 +162,64 @@ def pipe_records(m, b, nrhs_list, reps):
         torch.cuda.empty_cache()
 
 
+def form_q_records(m, n, b, reps):
+    """tqr_apply_pipe_form_q against the fill of an identity + tqr_apply_pipe_q / tqr_apply_q on it, fp64."""
+    import torch
+    cs = torch.cuda.current_stream()
+    A = torch.empty((n, m), dtype=torch.float64, device="cuda")
+    tau = torch.zeros((min(m, n) // b, m), dtype=torch.float64, device="cuda")
+    tqr.fill_randzo(A, m, n, 5)
+    plan = tqr.TiledQR(m, n, b, torch.float64)
+    plan.execute(A, tau)
+    plan.status()
+    ap = tqr.ApplyQ(m, n, b, torch.float64)
+    ap.prepare(A, tau, stream=cs)
+    del plan
+    p, kmax, ncols = m // b, min(m, n) // b, min(m, n)
+    nstrips = (ncols + 63) // 64
+    ops_full = nstrips * sum(p - k for k in range(kmax))
+    ops_form = sum((p - k) * (nstrips - k * b // 64) for k in range(kmax) if k * b <= ncols - 1)
+    pp = tqr.ApplyPipe(m, n, b, torch.float64, ncols)
+    Q = torch.full((ncols, m), float("nan"), dtype=torch.float64, device="cuda")
+    E = torch.empty((ncols, m), dtype=torch.float64, device="cuda")
+
+    def fill():
+        E.zero_()
+        E.fill_diagonal_(1.0)
+
+    calls = {"form_q": lambda: pp.form_q(ap, A, Q, stream=cs), "fill_identity": fill,
+             "apply_q_pipe_on_identity": lambda: ap.apply(A, E, trans=False, stream=cs, pipe=pp),
+             "apply_q_on_identity": lambda: ap.apply(A, E, trans=False, stream=cs)}
+    # the two results at this size (E holds the identity once more for every timed apply: the time of an
+    # apply does not depend on the values, but inf must not build up over the repetitions)
+    fill()
+    calls["form_q"]()
+    calls["apply_q_pipe_on_identity"]()
+    pp.status(cs)
+    same_values = bool(torch.equal(Q, E))
+    same_bytes = bool(torch.equal(Q.view(torch.int64), E.view(torch.int64)))
+    runs = {k: [] for k in calls}
+    order = ["form_q", "fill_identity", "apply_q_pipe_on_identity", "fill_identity", "apply_q_on_identity", "fill_identity"]
+    for name in order[:5]:  # warm-up: every call once
+        calls[name]()
+    torch.cuda.synchronize()
+    for _ in range(reps):  # alternating, so that drift hits every call alike
+        for name in order:
+            runs[name].append(round(timed(calls[name], 1, warm=False), 3))
+    pp.status(cs)
+    best = {k: min(v) for k, v in runs.items()}
+    rec = {"record": "formq", "dtype": "f64", "m": m, "n": n, "b": b, "ncols": ncols,
+           "items_form_q": tqr.apply_pipe_form_q_items(kmax, b, ncols), "items_apply_pipe": nstrips * kmax,
+           "tile_ops_form_q": ops_form, "tile_ops_apply": ops_full, "tile_ops_ratio": round(ops_form / ops_full, 4),
+           "values_equal": same_values, "bytes_equal": same_bytes,
+           **{k + "_ms": v for k, v in best.items()},
+           "form_q_over_fill_plus_pipe": round(best["form_q"] / (best["fill_identity"] + best["apply_q_pipe_on_identity"]), 4),
+           **{k + "_runs_ms": v for k, v in runs.items()}}
+    print(json.dumps(rec), flush=True)
+    del pp, ap, Q, E, A, tau
+    torch.cuda.empty_cache()
+
+
 def dapp_yardstick(b, want, reps):
     """(us per block, blocks) of one tqr_tile_batch DAPP launch of min(want, what fits) blocks."""
     L = tqr.lib()
@@ -193,6 +261,10 @@ def main(argv):
     reps, use_torch, shapes = parse(argv)
     assert torch.cuda.is_available(), "apply_bench.py measures on the GPU only"
     cs = torch.cuda.current_stream()
+    if FORMQ["on"]:
+        for m, b in shapes:
+            form_q_records(m, FORMQ["n"].get((m, b), m), b, reps)
+        return
     if PIPE["on"]:
         for m, b in shapes:
             pipe_records(m, b, PIPE["nrhs"], reps)
