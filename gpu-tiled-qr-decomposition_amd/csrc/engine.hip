@@ -1209,15 +1209,21 @@ static int cached_plan(int m, int n, int b, int dtype, PlanRef& ref, int engine 
   return TQR_OK;
 }
 
-int tqr_dgeqrt_tiled(int m, int n, int b, double* dA, int ldda, double* dtau, void* stream) {
+// Argument errors are refused here, before the cache is touched: a call that tqr_plan_execute would
+// refuse anyway must not first build (and keep) a plan, nor need a device to be told so.
+static int geqrt_tiled(int m, int n, int b, int dtype, void* dA, int ldda, void* dtau, void* stream) {
+  if (!dA || !dtau || !valid_b(b) || m <= 0 || n <= 0 || m % b || n % b || ldda < m ||
+      !valid_ld(ldda, dtype == TQR_F64 ? 8 : 4))
+    return TQR_EINVAL;
   PlanRef r;
-  int st = cached_plan(m, n, b, TQR_F64, r);
+  int st = cached_plan(m, n, b, dtype, r);
   return st ? st : tqr_plan_execute(r.pl, dA, ldda, dtau, stream);
 }
+int tqr_dgeqrt_tiled(int m, int n, int b, double* dA, int ldda, double* dtau, void* stream) {
+  return geqrt_tiled(m, n, b, TQR_F64, dA, ldda, dtau, stream);
+}
 int tqr_sgeqrt_tiled(int m, int n, int b, float* dA, int ldda, float* dtau, void* stream) {
-  PlanRef r;
-  int st = cached_plan(m, n, b, TQR_F32, r);
-  return st ? st : tqr_plan_execute(r.pl, dA, ldda, dtau, stream);
+  return geqrt_tiled(m, n, b, TQR_F32, dA, ldda, dtau, stream);
 }
 
 // Host-pointer factorisation (the reference's calling convention: cudaQRTask copies a host matrix

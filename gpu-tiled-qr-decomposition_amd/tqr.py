@@ -69,6 +69,16 @@ def lib():
     L.tqr_plan_create.argtypes = [ctypes.POINTER(_P), _I, _I, _I, _I]
     L.tqr_plan_create_steps.argtypes = [ctypes.POINTER(_P), _I, _I, _I, _I, _I]
     L.tqr_plan_create_steps.restype = _I
+    L.tqr_plan_create_engine.argtypes = [ctypes.POINTER(_P), _I, _I, _I, _I, _I]
+    L.tqr_plan_create_engine.restype = _I
+    L.tqr_plan_info.argtypes = [_P, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]
+    L.tqr_plan_info.restype = _I
+    L.tqr_plan_set_tasks.argtypes = [_P, _P, _I]
+    L.tqr_plan_set_tasks.restype = _I
+    L.tqr_plan_debug_workspace.argtypes = [_P, _I, _P, ctypes.c_size_t]
+    L.tqr_plan_debug_workspace.restype = _I
+    L.cudaQRFull.argtypes = [_P, _I, _I]
+    L.cudaQRFull.restype = None
     L.tqr_plan_steps.argtypes = [_P]
     L.tqr_plan_steps.restype = _I
     L.tqr_plan_execute.argtypes = [_P, _P, _I, _P, _P]
@@ -92,6 +102,12 @@ def lib():
     L.tqr_dist_owner.argtypes = [_P, _I]
     L.tqr_dgeqrt_host.argtypes = [_P, _P, _I, _I, _I, _I]
     L.tqr_sgeqrt_host.argtypes = [_P, _P, _I, _I, _I, _I]
+    L.tqr_geqrt_host_engine.argtypes = [_I, _P, _P, _I, _I, _I, _I, _I]
+    L.tqr_geqrt_host_engine.restype = _I
+    L.tqr_dgeqrt_tiled.argtypes = [_I, _I, _I, _P, _I, _P, _P]
+    L.tqr_dgeqrt_tiled.restype = _I
+    L.tqr_sgeqrt_tiled.argtypes = [_I, _I, _I, _P, _I, _P, _P]
+    L.tqr_sgeqrt_tiled.restype = _I
     L.tqr_flow_list_export.argtypes = [_P, _P, _I]
     L.tqr_flow_list_export_steps.argtypes = [_P, _I, _P, _I]
     L.tqr_flow_list_export_steps.restype = _I
@@ -205,17 +221,30 @@ def sched_plan(M, N):
 
 
 # ---- device factorisation -------------------------------------------------------------------
+ENGINES = {"waves": 0, "flow": 1}  # tqr_engine (include/tqr.h)
+
+
 class TiledQR:
     """A planned factorisation (tqr_plan): create once, execute on device arrays. steps: a capped
     plan (tqr_plan_create_steps) — only the leading `steps` tile columns are factorised, every other
-    column receives Q^T of those steps; tau is then (steps, m)."""
+    column receives Q^T of those steps; tau is then (steps, m). engine: None (tqr_plan_create: the
+    flow engine unless TQR_ENGINE=waves), or "flow" / "waves" (tqr_plan_create_engine); a capped plan
+    always runs the flow engine, so engine together with steps raises."""
 
-    def __init__(self, m, n, b, dtype, steps=None):
+    def __init__(self, m, n, b, dtype, steps=None, engine=None):
         self.m, self.n, self.b = m, n, b
         self.dtype = dtype if isinstance(dtype, int) else _dtype_code(dtype)
         self.h = None
+        if engine is not None and engine not in ENGINES:
+            raise TQRError(f"TiledQR: engine must be None, 'flow' or 'waves', not {engine!r}")
+        if engine is not None and steps is not None:
+            raise TQRError("TiledQR: a capped plan (steps) always runs the flow engine; engine= cannot be given with it")
         h = _P()
-        if steps is None:
+        if engine is not None:
+            self.kmax = min(m, n) // b
+            check(lib().tqr_plan_create_engine(ctypes.byref(h), m, n, b, self.dtype, ENGINES[engine]),
+                  "tqr_plan_create_engine")
+        elif steps is None:
             self.kmax = min(m, n) // b
             check(lib().tqr_plan_create(ctypes.byref(h), m, n, b, self.dtype), "tqr_plan_create")
         else:
@@ -439,26 +468,54 @@ def flow_list(M, N, b, dtype=TQR_F64, seglen=0, world=1, rank=-1, full=1, nxc=0,
     return items
 
 
+def plan_info(plan):
+    """tqr_plan_info of a TiledQR: engine (0 waves, 1 flow), ntasks, est_order, grid."""
+    v = [_I() for _ in range(4)]
+    check(lib().tqr_plan_info(plan.h, *[ctypes.byref(x) for x in v]), "tqr_plan_info")
+    return dict(zip(("engine", "ntasks", "est_order", "grid"), (x.value for x in v)))
+
+
 def fill_randzo(A, m, n, seed, ldda=None, stream=None, col0=0):
     """RANDZO input on the device (columns col0 .. col0 + n - 1 of the global matrix)."""
     check(lib().tqr_fill_randzo_cols(_dtype_code(A.dtype), _ptr(A), m, n, ldda or m, seed, col0, _P(stream or 0)),
           "tqr_fill_randzo_cols")
 
 
-def geqrt_host(A, b, with_tau=True, m=None, tau=None):
+def geqrt_host(A, b, with_tau=True, m=None, tau=None, engine=None):
     """Factorise a host column-major array (shape (n, ldm)) in place on the GPU; returns the
     reference's m x n tau matrix (shape (n, ldm), zero except columns k*b; written into `tau` if
     given, else a new zeroed array), or None with with_tau=False (the reference's cudaQRTask
-    discards tau). m: rows (default ldm)."""
+    discards tau). m: rows (default ldm). engine: None (tqr_dgeqrt_host / tqr_sgeqrt_host), or
+    "flow" / "waves" (tqr_geqrt_host_engine)."""
     n, ldm = A.shape
     m = m or ldm
     if with_tau and tau is None:
         tau = np.zeros_like(A)
     if with_tau:
         assert tau.shape == A.shape and tau.dtype == A.dtype and tau.flags.c_contiguous
+    ptau = _ptr(tau) if with_tau else None
+    if engine is not None:
+        if engine not in ENGINES:
+            raise TQRError(f"geqrt_host: engine must be None, 'flow' or 'waves', not {engine!r}")
+        check(lib().tqr_geqrt_host_engine(_dtype_code(A.dtype), _ptr(A), ptau, m, n, ldm, b, ENGINES[engine]),
+              "tqr_geqrt_host_engine")
+        return tau
     fn = lib().tqr_dgeqrt_host if A.dtype == np.float64 else lib().tqr_sgeqrt_host
-    check(fn(_ptr(A), _ptr(tau) if with_tau else None, m, n, ldm, b), "tqr_geqrt_host")
+    check(fn(_ptr(A), ptau, m, n, ldm, b), "tqr_geqrt_host")
     return tau
+
+
+def geqrt_tiled(A, tau, b, m=None, ldda=None, stream=None):
+    """The cached one-shot device helper (tqr_dgeqrt_tiled / tqr_sgeqrt_tiled by A's dtype): A
+    (n, ldda) and tau (kmax, m) are device tensors of one dtype, factorised in place with the plan
+    cached for (device, m, n, b, dtype). m defaults to ldda, ldda to A's row length. Stream-ordered."""
+    n = A.shape[0]
+    ldda = ldda or A.shape[-1]
+    m = m or ldda
+    if tau.dtype != A.dtype:
+        raise TQRError("geqrt_tiled: A and tau must be of one dtype")
+    fn = lib().tqr_dgeqrt_tiled if _dtype_code(A.dtype) == TQR_F64 else lib().tqr_sgeqrt_tiled
+    check(fn(m, n, b, _ptr(A), ldda, _ptr(tau), _stream_handle(stream)), "tqr_geqrt_tiled")
 
 
 def cache_clear():

@@ -45,7 +45,15 @@ typedef struct tqr_plan tqr_plan;
 /* Plan a factorisation of an m x n matrix of `dtype` with tile size b on the current HIP
  * device. */
 int tqr_plan_create(tqr_plan** plan, int m, int n, int b, int dtype);
-/* Execution engines (both compute the same factorisation, bit for bit per tile operation):
+/* Execution engines. Both compute the same factorisation — the same tile operations over the same
+ * DAG, each within the project's bound of the reference (fp64 1e-11 scaled, fp32 1e-3) — but with
+ * different kernels: reflector-group sizes and summation orders inside a tile operation differ (and
+ * fp32 storage runs fp32 MFMA chains in the flow engine only), so their results agree to rounding,
+ * NOT in bits. Measured on an MI355X on Gaussian inputs from 64 x 64, b = 16 to 768 x 768, b = 256, in
+ * both dtypes: 70 - 95 % of the entries of the factorised matrix and about half of the written taus
+ * differ in their last bits (max difference 7e-14 fp64, 6e-5 fp32; DESIGN.md §4.1 has the counts).
+ * Each engine on its own is bit-reproducible: the bits do not depend on ldda, the base address, the
+ * stream, the profile switch, or on which threads and streams share the plan.
  *   TQR_ENGINE_FLOW  — one persistent dataflow launch: workgroups pull GEQRT/TSQRT panel tasks
  *                      and fused UNMQR/TSMQR column chains from a static topological list and
  *                      synchronise through progress counters (default);
@@ -466,7 +474,11 @@ int tqr_dist_plan_check(int M, int N, int b, int seglen, int rank, int world, in
 
 /* ---- one-shot helpers ------------------------------------------------------------------ */
 /* Device pointers, stream-ordered; plan cached per (device,m,n,b,dtype) and shared by all
- * callers — concurrent calls with the same shape are serialised on the GPU (see execute). */
+ * callers — concurrent calls with the same shape are serialised on the GPU (see execute). The
+ * result has the bits of tqr_plan_execute on a plan of one's own. The cached plan's engine is
+ * TQR_ENGINE_DEFAULT's at the time the plan is created (the first call for a shape, or the first
+ * after tqr_cache_clear). Argument errors (sizes, tile size, NULL pointers, ldda < m or beyond the
+ * leading-dimension bound) return TQR_EINVAL before the cache or a device is touched. */
 int tqr_dgeqrt_tiled(int m, int n, int b, double* dA, int ldda, double* dtau_compact, void* stream);
 int tqr_sgeqrt_tiled(int m, int n, int b, float* dA, int ldda, float* dtau_compact, void* stream);
 

@@ -19,6 +19,13 @@ SHAPES = [(96, 64, 32), (192, 128, 64), (384, 256, 128), (768, 512, 256), (256, 
 SHAPES32 = [(192, 128, 64), (768, 512, 256)]
 ACC_SHAPES = [(192, 128, 64), (768, 512, 256)]
 FAMILIES = ["gauss", "rowgraded", "cond1e8"]
+# the wave engine's shapes (test_gpu_waves.py), both dtypes at each: 4 x 4, 4 x 4, 4 x 3, 4 x 3 and 3 x 3
+# tiles and a wide 2 x 4. Every tile size, so k_update's strip counts 1, 1, 1, 2, 4 and the reflector-group
+# counts 1, 1, 2, 4, 8; p, q >= 3 (all but the wide one) puts the panel tasks of step k+1 into one wave
+# with update tasks of step k. The smallest shapes with those properties.
+WAVE_SHAPES = [(64, 64, 16), (128, 128, 32), (256, 192, 64), (512, 384, 128), (768, 768, 256), (128, 256, 64)]
+WAVE_ACC_SHAPES = [(64, 64, 16), (256, 192, 64), (768, 768, 256)]
+WAVE_ACC_SHAPES32 = [(256, 192, 64), (768, 768, 256)]
 KMAX = {np.dtype(np.float64): 400, np.dtype(np.float32): 30}  # column exponents of scaling()
 # shapes of the apply / solve tests on these inputs (test_gpu_solve_inputs.py and its CPU twin)
 SOLVE_CASES = [((96, 64, 32), np.float64), ((192, 128, 64), np.float64), ((768, 512, 256), np.float64),

@@ -71,6 +71,33 @@ def test_invalid_engine_and_batch_args_without_gpu(tqr):
     assert L.tqr_plan_execute(None, None, 0, None, None) == -1
 
 
+def test_engine_arguments_of_the_python_mirror_without_gpu(tqr):
+    """tqr.TiledQR(engine=...) and tqr.geqrt_host(engine=...): a name outside {"flow", "waves"}, and
+    engine together with steps (a capped plan always runs the flow engine), raise before any call into
+    the library; the engine codes are tqr.h's."""
+    import numpy as np
+    import pytest
+    assert tqr.ENGINES == {"waves": 0, "flow": 1}
+    with pytest.raises(tqr.TQRError, match="engine"):
+        tqr.TiledQR(256, 256, 64, np.float64, engine="wave")
+    for engine in ("flow", "waves"):
+        with pytest.raises(tqr.TQRError, match="capped"):
+            tqr.TiledQR(256, 256, 64, np.float64, steps=2, engine=engine)
+    A = np.zeros((64, 64))
+    with pytest.raises(tqr.TQRError, match="engine"):
+        tqr.geqrt_host(A, 16, engine=0)
+    assert not A.any()
+    # arguments the library itself refuses before it needs a device, through the new bindings
+    for engine in ("flow", "waves"):
+        with pytest.raises(tqr.TQRError, match="invalid argument"):
+            tqr.TiledQR(100, 64, 32, np.float64, engine=engine)
+        with pytest.raises(tqr.TQRError, match="invalid argument"):
+            tqr.geqrt_host(np.zeros((64, 100)), 32, engine=engine)
+    L = tqr.lib()
+    assert L.tqr_dgeqrt_tiled(0, 64, 32, None, 64, None, None) == -1
+    assert L.tqr_sgeqrt_tiled(64, 64, 24, None, 64, None, None) == -1
+
+
 def test_flow_plan_export(tqr):
     """The persistent engine's task list (host only): every panel member and chain segment once."""
     import ctypes

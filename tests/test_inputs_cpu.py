@@ -7,9 +7,11 @@ import numpy as np
 import pytest
 
 import inputs
-from inputs import ACC_SHAPES, FAMILIES, SHAPES, SHAPES32, dtname
+from inputs import ACC_SHAPES, FAMILIES, SHAPES, SHAPES32, WAVE_ACC_SHAPES, WAVE_ACC_SHAPES32, WAVE_SHAPES, dtname
 
-SCALE_CASES = [(s, np.float64) for s in SHAPES] + [(s, np.float32) for s in SHAPES32]
+# (the wave engine's shapes, test_gpu_waves.py, run in both dtypes at every shape)
+SCALE_CASES = [(s, np.float64) for s in SHAPES] + [(s, np.float32) for s in SHAPES32] + \
+              [(s, dt) for s in WAVE_SHAPES for dt in (np.float64, np.float32)]
 
 
 @pytest.mark.parametrize("shape,dt", SCALE_CASES, ids=[f"{m}x{n}b{b}-{dtname(dt)}" for (m, n, b), dt in SCALE_CASES])
@@ -17,6 +19,7 @@ def test_oracle_column_scaling_bitexact(oracle, shape, dt):
     A = inputs.matrix("gauss", shape, dt)
     d = inputs.scaling(shape, dt)
     assert np.abs(A).min() > 0  # no zero pivot: sign(x0) flips with the column
+    assert inputs.in_normal_range(inputs.scale_columns(A, d))  # the scaling itself is exact
     F, T = inputs.oracle_factor(oracle, "gauss", shape, dt)
     Fs, Ts = oracle.factor(inputs.scale_columns(A, d), shape[2])
     inputs.assert_covariant(F, T, Fs, Ts, d)
@@ -58,7 +61,7 @@ def test_qr_longdouble_small():
     assert np.all(np.tril(R, -1) == 0)
 
 
-@pytest.mark.parametrize("shape", ACC_SHAPES, ids=lambda s: "%dx%db%d" % s)
+@pytest.mark.parametrize("shape", ACC_SHAPES + WAVE_ACC_SHAPES, ids=lambda s: "%dx%db%d" % s)
 @pytest.mark.parametrize("family", FAMILIES)
 def test_oracle_accuracy(oracle, family, shape):
     if not inputs.have_longdouble():
@@ -72,3 +75,15 @@ def test_oracle_accuracy(oracle, family, shape):
     assert res <= 1e-13
     assert cn <= 1e-12
     assert np.isfinite(e) and e < 1e-13
+
+
+@pytest.mark.parametrize("shape", WAVE_ACC_SHAPES32, ids=lambda s: "%dx%db%d" % s)
+def test_oracle_fp32_reference_error(oracle, shape):
+    """test_gpu_waves.py bounds the fp32 wave engine by 1.5 x the fp32 oracle's distance from the fp64
+    oracle on the same fp32-valued input: that distance is a positive number far inside the 1e-4 scale."""
+    A = inputs.matrix("gauss", shape, np.float32)
+    F32, _ = inputs.oracle_factor(oracle, "gauss", shape, np.float32)
+    F64, _ = oracle.factor(A.astype(np.float64), shape[2])
+    e_ref = float(np.abs(F32 - F64).max())
+    print(f"fp32 gauss {shape}: fp32 oracle vs fp64 oracle {e_ref:.3e} (max|F| {np.abs(F32).max():.3e})")
+    assert 0 < e_ref <= 1e-4 * max(1.0, float(np.abs(F32).max()))
