@@ -16,13 +16,12 @@
 // runs the same tile operations with one workgroup per (strip, step) on them.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstring>
 #include <mutex>
 #include <new>
 
 #include "apply.hpp"
 #include "apply_dev.hpp"
+#include "host_common.hpp"
 #include "solve.hpp"
 #include "tqr.h"
 
@@ -170,15 +169,6 @@ static_assert(Geo<256>::TIMG == 1152 && Geo<16>::TIMG == 384, "host timg_doubles
 
 using namespace tqr;
 
-#define HIPCHK(x)                                                                         \
-  do {                                                                                    \
-    hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess) {                                                               \
-      fprintf(stderr, "tqr: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); \
-      return TQR_EHIP;                                                                    \
-    }                                                                                     \
-  } while (0)
-
 extern "C" {
 
 void tqr_apply_destroy(tqr_apply* ap) {
@@ -193,31 +183,22 @@ void tqr_apply_destroy(tqr_apply* ap) {
 int tqr_apply_create(tqr_apply** out, int m, int n, int b, int dtype) {
   if (!out) return TQR_EINVAL;
   *out = nullptr;
-  if (!apply_valid_b(b) || m <= 0 || n <= 0 || m % b || n % b || (dtype != TQR_F32 && dtype != TQR_F64) ||
-      !apply_valid_ld(m, dtype == TQR_F64 ? 8 : 4))
+  if (!valid_b(b) || m <= 0 || n <= 0 || m % b || n % b || (dtype != TQR_F32 && dtype != TQR_F64) ||
+      !valid_ld(m, elem_size(dtype)))
     return TQR_EINVAL;
-  int dev = 0;
-  hipDeviceProp_t pr;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) return TQR_ENODEV;
-  if (strncmp(pr.gcnArchName, "gfx950", 6) != 0) {
-    fprintf(stderr, "tqr: device %d is %s, this build targets gfx950 only\n", dev, pr.gcnArchName);
-    return TQR_ENODEV;
-  }
+  if (const int st = current_device_is_gfx950()) return st;
   tqr_apply* ap = new (std::nothrow) tqr_apply();
   if (!ap) return TQR_ENOMEM;
   ap->m = m; ap->n = n; ap->b = b; ap->p = m / b; ap->q = n / b;
   ap->kmax = ap->p < ap->q ? ap->p : ap->q;
   ap->dtype = dtype;
-  ap->es = dtype == TQR_F64 ? 8 : 4;
+  ap->es = elem_size(dtype);
   const size_t ntiles = tile_slot(ap->kmax, ap->kmax, ap->p);  // tiles (l,k), l >= k, k < kmax
   ap->ws_bytes = ntiles * (size_t)(b / (b < 32 ? b : 32)) * timg_doubles(b) * sizeof(double);
-#define TQR_K(BB)                                                                   \
-  case BB:                                                                          \
-    if (dtype == TQR_F64) apply_kernels<BB, double>(&ap->kt, &ap->kqt, &ap->kqn);   \
-    else apply_kernels<BB, float>(&ap->kt, &ap->kqt, &ap->kqn);                     \
-    break;
-  switch (b) { TQR_K(16) TQR_K(32) TQR_K(64) TQR_K(128) TQR_K(256) }
-#undef TQR_K
+  dispatch_b(b, [&](auto bb) {
+    if (dtype == TQR_F64) apply_kernels<decltype(bb)::value, double>(&ap->kt, &ap->kqt, &ap->kqn);
+    else apply_kernels<decltype(bb)::value, float>(&ap->kt, &ap->kqt, &ap->kqn);
+  });
   if (hipFuncSetAttribute((const void*)ap->kt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_apply_t(b)) != hipSuccess ||
       hipFuncSetAttribute((const void*)ap->kqt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_apply_q(b)) != hipSuccess ||
       hipFuncSetAttribute((const void*)ap->kqn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_apply_q(b)) != hipSuccess) {
@@ -243,7 +224,7 @@ int tqr_apply_create(tqr_apply** out, int m, int n, int b, int dtype) {
 size_t tqr_apply_workspace_bytes(const tqr_apply* ap) { return ap ? ap->ws_bytes : 0; }
 
 int tqr_apply_prepare(tqr_apply* ap, const void* dA, int ldda, const void* dtau, void* stream) {
-  if (!ap || !dA || !dtau || ldda < ap->m || !apply_valid_ld(ldda, ap->es)) return TQR_EINVAL;
+  if (!ap || !dA || !dtau || ldda < ap->m || !valid_ld(ldda, ap->es)) return TQR_EINVAL;
   hipStream_t cs = (hipStream_t)stream;
   std::lock_guard<std::mutex> lk(ap->mu);
   // the workspace is rewritten: wait for every apply enqueued since the last prepare
@@ -263,8 +244,8 @@ int tqr_apply_prepare(tqr_apply* ap, const void* dA, int ldda, const void* dtau,
 }
 
 int tqr_apply_q(tqr_apply* ap, int trans, const void* dA, int ldda, void* dC, int nrhs, int lddc, void* stream) {
-  if (!ap || !dA || !dC || nrhs < 1 || ldda < ap->m || lddc < ap->m || !apply_valid_ld(ldda, ap->es) ||
-      !apply_valid_ld(lddc, ap->es) || (trans != TQR_NOTRANS && trans != TQR_TRANS))
+  if (!ap || !dA || !dC || nrhs < 1 || ldda < ap->m || lddc < ap->m || !valid_ld(ldda, ap->es) ||
+      !valid_ld(lddc, ap->es) || (trans != TQR_NOTRANS && trans != TQR_TRANS))
     return TQR_EINVAL;
   hipStream_t cs = (hipStream_t)stream;
   std::lock_guard<std::mutex> lk(ap->mu);
@@ -286,8 +267,8 @@ int tqr_apply_q(tqr_apply* ap, int trans, const void* dA, int ldda, void* dC, in
 // only (not the T workspace), so it needs none of the handle's events.
 int tqr_lstsq(tqr_apply* ap, int trans, const void* dA, int ldda, void* dB, int nrhs, int lddb, void* dres,
               void* stream) {
-  if (!ap || !dA || !dB || nrhs < 1 || ap->m < ap->n || ldda < ap->m || lddb < ap->m || !apply_valid_ld(ldda, ap->es) ||
-      !apply_valid_ld(lddb, ap->es) || (trans != TQR_NOTRANS && trans != TQR_TRANS))
+  if (!ap || !dA || !dB || nrhs < 1 || ap->m < ap->n || ldda < ap->m || lddb < ap->m || !valid_ld(ldda, ap->es) ||
+      !valid_ld(lddb, ap->es) || (trans != TQR_NOTRANS && trans != TQR_TRANS))
     return TQR_EINVAL;
   {
     std::lock_guard<std::mutex> lk(ap->mu);

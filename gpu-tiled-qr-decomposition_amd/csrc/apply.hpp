@@ -1,6 +1,5 @@
 // Host side of the apply handle (include/tqr.h "apply"), shared by apply.hip (tqr_apply_*, tqr_lstsq)
-// and apply_pipe.hip (tqr_apply_pipe_*, tqr_lstsq_pipe): the handle itself, the argument checks, and
-// the event bookkeeping that orders every apply of a handle against its prepares.
+// and apply_pipe.hip (tqr_apply_pipe_*, tqr_lstsq_pipe): the handle itself and the event bookkeeping that orders every apply of a handle against its prepares.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,10 +9,6 @@ namespace tqr {
 
 struct ApplyArgs;
 typedef void (*afn)(ApplyArgs);
-
-static inline bool apply_valid_b(int b) { return b == 16 || b == 32 || b == 64 || b == 128 || b == 256; }
-// the library's leading-dimension bound (include/tqr.h): 32 * ld * sizeof(element) < 2^31
-static inline bool apply_valid_ld(long ld, size_t es) { return ld > 0 && (size_t)32 * (size_t)ld * es <= 0x7fffffffull; }
 
 // applies of one handle on up to NSLOT distinct streams are tracked one event each, so that a
 // later prepare can wait for all of them; further streams share slot 0 (and are ordered behind

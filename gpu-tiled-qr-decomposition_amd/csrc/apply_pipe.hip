@@ -17,26 +17,11 @@
 // through memory between two of them exactly where it does there (fp32 storage: rounded to float at
 // every store), so the critical path is about p + 2 kmax tile operations instead of all of them.
 //
-// Protocol between workgroups (MI355X_MICROARCH.md "Workgroup dispatch ... inter-workgroup
-// visibility", "Valid forms", first table row; solve_pipe.hip's form):
-//   * work items come from one atomic ticket counter, never from blockIdx: ticket t is (strip, step)
-//     by apply_ticket_map, and the only producer of (strip, k), which is (strip, k-1) for Q^T and
-//     (strip, k+1) for Q, has a smaller ticket. A workgroup that waits holds a ticket, so what it waits
-//     for was taken by a workgroup already running, whatever the dispatch order and however few
-//     workgroups are resident;
-//   * every load and store of C in this kernel is an sc1 buffer access (L1-bypassing / write-through),
-//     the workgroup's own rows included: every byte of C was stored or will be loaded by another
-//     workgroup. V, T and tau come from earlier launches: plain loads. To publish, each wave drains
-//     (s_waitcnt vmcnt(0)), the workgroup meets at a barrier, and one lane stores the flag (sc1). A
-//     consumer's thread 0 polls the flag with sc1 loads and s_sleep; the other waves load the row tile
-//     only behind the barrier thread 0 then joins;
-//   * the table row holds at one workgroup per CU: the launch asks for PIPE_LDS bytes of LDS;
-//   * a flag holds the epoch of the call that set it and a call waits for its own epoch, so nothing
-//     is reset between calls; the ticket counter is zeroed by a memset ahead of each launch, and the
-//     calls of one handle are serialised by an event;
-//   * every spin is bounded (PIPE_TIMEOUT): on expiry the error word is set, the workgroup leaves
-//     without publishing, and every workgroup that sees the word — in a spin or before it takes a
-//     ticket — leaves too. tqr_apply_pipe_status reports it.
+// The protocol between the workgroups — tickets, sc1 hand-over, epoch flags, bounded waits — is
+// pipe_dev.hpp's. Here a work item is (strip, step) by pipe_ticket_map over the kmax steps, and the only
+// producer of (strip, k) is (strip, k-1) for Q^T and (strip, k+1) for Q. Every load and store of C is an
+// sc1 access, the workgroup's own rows included: every byte of C was stored or will be loaded by another
+// workgroup. V, T and tau come from earlier launches: plain loads.
 //
 // k_form_q_pipe (tqr_apply_pipe_form_q) is the Q direction of the same on the first ncols columns of an
 // identity that is never stored: only the (strip, step) items that meet non-zero data exist
@@ -44,28 +29,18 @@
 // flags, hand-over, bounded waits and handle.
 #include <hip/hip_runtime.h>
 
-#include <climits>
-#include <cstdio>
-#include <cstring>
 #include <mutex>
 #include <new>
 
 #include "apply.hpp"
 #include "apply_dev.hpp"
+#include "host_common.hpp"
 #include "pipe_dev.hpp"
+#include "pipe_host.hpp"
 #include "solve.hpp"
 #include "tqr.h"
 
 namespace tqr {
-
-// Work item of ticket t on kmax steps x nstrips strips: tickets go step by step in the order the
-// apply needs them (Q^T: step 0 first; Q: step kmax-1 first), all strips of a step side by side — so
-// the producer of (strip, step), the step before it in the same strip, has a smaller ticket.
-__host__ __device__ inline void apply_ticket_map(int kmax, int nstrips, bool trans, int t, int* strip, int* step) {
-  const int pos = t / nstrips;
-  *strip = t - pos * nstrips;
-  *step = trans ? pos : kmax - 1 - pos;
-}
 
 // ---------------------------------------------------------------------------------------
 // Form Q (tqr_apply_pipe_form_q): Q applied to E = the first ncols columns of I_m, without the work on
@@ -79,7 +54,7 @@ __host__ __device__ inline int form_q_steps(int kmax, int b, int ncols) {
   const int ka = (ncols - 1) / b + 1;
   return ka < kmax ? ka : kmax;
 }
-// Work item of ticket t: tickets go step-descending as apply_ticket_map's for Q, over the active
+// Work item of ticket t: tickets go step-descending as pipe_ticket_map's for Q, over the active
 // strips of each step only — so the one producer of (strip, step), which is (strip, step + 1) where step
 // < kf(strip), has a smaller ticket. False: t is no ticket (t >= the item count). The search walks at
 // most kmax counts, once per workgroup, in scalar registers that are free again before the tile loops.
@@ -126,13 +101,10 @@ __global__ __launch_bounds__(NT) void k_apply_q_pipe(ApplyPipeArgs pa) {
   __shared__ int s_tk, s_ok;
   const ApplyArgs& a = pa.q;
 
-  if (threadIdx.x == 0)
-    s_tk = ld_sc1(pa.ws + PIPE_ERR) ? -1 : __hip_atomic_fetch_add((pint*)(pa.ws + PIPE_TICKET), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  const int tk = __builtin_amdgcn_readfirstlane(s_tk), nstrips = (a.nrhs + 63) >> 6;
+  const int tk = pipe_take_ticket(pa.ws, &s_tk), nstrips = (a.nrhs + 63) >> 6;
   if (tk < 0 || tk >= a.kmax * nstrips) return;  // (an earlier call of the handle timed out: tqr_apply_pipe_status)
   int strip, k;
-  apply_ticket_map(a.kmax, nstrips, TRANS, tk, &strip, &k);
+  pipe_ticket_map(a.kmax, nstrips, TRANS, tk, &strip, &k);
 
   const size_t ldc = a.ldc;
   const int lane = threadIdx.x & 63, x = lane >> 4, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -176,18 +148,9 @@ __global__ __launch_bounds__(NT) void k_apply_q_pipe(ApplyPipeArgs pa) {
   asm volatile("" : "+v"(fmine), "+v"(fprod));
   // all threads: the producing step has released row tile l of this strip in this call (false: error
   // or timeout, uniform)
-  auto wait = [&](int l) {
-    if (threadIdx.x == 0) s_ok = pipe_spin_ge((int*)fprod + l, epoch, (int*)errv) ? 1 : 0;
-    __syncthreads();
-    // (thread 0 rewrites s_ok only behind the next barrier, which every thread reaches after this read)
-    return s_ok != 0;
-  };
-  // release row tile l: every wave's stores drained, a barrier, one lane's flag store
-  auto publish = [&](int l) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store((pint*)((int*)fmine + l), epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
+  auto wait = [&](int l) { return pipe_wait((int*)fprod + l, epoch, (int*)errv, &s_ok); };
+  // release row tile l
+  auto publish = [&](int l) { pipe_publish((int*)fmine + l, epoch); };
   // k_apply_q's unmqr(k): tile (k,k) on C_k, groups ascending (Q^T) / descending (Q)
   auto unmqr = [&](const bool active) {
     const S* Vt = Ak + (size_t)k * B;
@@ -256,8 +219,13 @@ __global__ __launch_bounds__(NT) void k_apply_q_pipe(ApplyPipeArgs pa) {
 // operands; what differs is where a row tile's values come from the first time the call touches it:
 // E's 0 / 1 pattern built in registers (synth_rows) instead of load_rows. That is C_k in every step —
 // no step above k touches row tile k — and every C_l in the strip's first step kf, which therefore
-// waits for nothing. A sibling kernel, not a template flag: k_apply_q_pipe's text and code stay as
-// they were.
+// waits for nothing. A sibling kernel, not a template flag, for a measured reason: one body for both
+// (a forceinline function template with a FORM flag, the two kernels one-line callers) kept every
+// instantiation free of scratch and spills and within 4 VGPRs, but changed k_apply_q_pipe's register
+// allocation and instruction order, and k_apply_q_pipe<256, double, false> came out 0.3 - 0.4 % slower
+// than before on an MI355X, beyond its run-to-run spread, with the body's arguments by reference and
+// by value alike (profiles/apply/refactor_ab.jsonl). The two share the protocol through
+// pipe_dev.hpp's helpers only.
 // ---------------------------------------------------------------------------------------
 // stage_vq<B, S, false, true> (a TSMQR tile's V group, columns reversed: the same image) with the batch
 // written out: up to eight loads issued, then their LDS writes, a scheduling barrier in between. In
@@ -303,10 +271,7 @@ __global__ __launch_bounds__(NT) void k_form_q_pipe(ApplyPipeArgs pa) {
   __shared__ int s_tk, s_ok;
   const ApplyArgs& a = pa.q;
 
-  if (threadIdx.x == 0)
-    s_tk = ld_sc1(pa.ws + PIPE_ERR) ? -1 : __hip_atomic_fetch_add((pint*)(pa.ws + PIPE_TICKET), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  const int tk = __builtin_amdgcn_readfirstlane(s_tk);
+  const int tk = pipe_take_ticket(pa.ws, &s_tk);
   int strip, k;
   if (tk < 0 || !form_q_ticket_map(a.kmax, B, a.nrhs, tk, &strip, &k)) return;  // (tk < 0: k_apply_q_pipe)
   // the strip's first step kf = min(jhi, kmax - 1), jhi the row tile of its last column
@@ -341,16 +306,8 @@ __global__ __launch_bounds__(NT) void k_form_q_pipe(ApplyPipeArgs pa) {
   unsigned long long fmine = flv + (unsigned long long)((long long)tile_slot(k, k, a.p) - k) * sizeof(int);
   unsigned long long fprod = flv + (unsigned long long)((long long)tile_slot(k + 1, k + 1, a.p) - (k + 1)) * sizeof(int);
   asm volatile("" : "+v"(fmine), "+v"(fprod));
-  auto wait = [&](int l) {
-    if (threadIdx.x == 0) s_ok = pipe_spin_ge((int*)fprod + l, epoch, (int*)errv) ? 1 : 0;
-    __syncthreads();
-    return s_ok != 0;
-  };
-  auto publish = [&](int l) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store((pint*)((int*)fmine + l), epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
+  auto wait = [&](int l) { return pipe_wait((int*)fprod + l, epoch, (int*)errv, &s_ok); };
+  auto publish = [&](int l) { pipe_publish((int*)fmine + l, epoch); };
   // E's values in the lane's rows of row tile l: 1.0 where the global row equals the global column,
   // +0.0 elsewhere and in a masked lane (load_rows' zeros)
   auto synth_rows = [&](int l) {
@@ -422,36 +379,15 @@ static apfn apipe_kernel(int dtype, int trans) {
   return trans == TQR_TRANS ? k_apply_q_pipe<B, float, true> : k_apply_q_pipe<B, float, false>;
 }
 static apfn apipe_kernel_b(int b, int dtype, int trans) {
-  switch (b) {
-    case 16: return apipe_kernel<16>(dtype, trans);
-    case 32: return apipe_kernel<32>(dtype, trans);
-    case 64: return apipe_kernel<64>(dtype, trans);
-    case 128: return apipe_kernel<128>(dtype, trans);
-    default: return apipe_kernel<256>(dtype, trans);
-  }
+  return dispatch_b(b, [&](auto bb) { return apipe_kernel<decltype(bb)::value>(dtype, trans); });
 }
 template <int B>
 static apfn aform_kernel(int dtype) {
   return dtype == TQR_F64 ? k_form_q_pipe<B, double> : k_form_q_pipe<B, float>;
 }
 static apfn aform_kernel_b(int b, int dtype) {
-  switch (b) {
-    case 16: return aform_kernel<16>(dtype);
-    case 32: return aform_kernel<32>(dtype);
-    case 64: return aform_kernel<64>(dtype);
-    case 128: return aform_kernel<128>(dtype);
-    default: return aform_kernel<256>(dtype);
-  }
+  return dispatch_b(b, [&](auto bb) { return aform_kernel<decltype(bb)::value>(dtype); });
 }
-
-#define HIPCHK(x)                                                                         \
-  do {                                                                                    \
-    hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess) {                                                               \
-      fprintf(stderr, "tqr: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); \
-      return TQR_EHIP;                                                                    \
-    }                                                                                     \
-  } while (0)
 
 }  // namespace tqr
 
@@ -459,51 +395,17 @@ using namespace tqr;
 
 struct tqr_apply_pipe {
   int m, n, b, p, kmax, dtype, nrhs_max;
-  size_t es, ws_bytes;
+  size_t es;
   long long nslot;  // flags per strip
   apfn kn = nullptr, kt = nullptr, kf = nullptr;  // Q, Q^T, form-Q
-  std::mutex mu;        // the enqueue sequence of a call (epoch, event bookkeeping)
-  int* d_ws = nullptr;  // device workspace (null until a gfx950 was seen)
-  hipEvent_t evDone = nullptr;
-  int epoch = 0;
+  PipeCore core;
 };
-
-// The handle's device side, made on first need (tqr_apply_pipe_create where a device is present): the
-// zeroed workspace, the event and the kernels' LDS attribute. mu held, or the handle not yet shared.
-static int apply_pipe_ready(tqr_apply_pipe* pp) {
-  if (pp->d_ws) return TQR_OK;
-  int dev = 0;
-  hipDeviceProp_t pr;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) {
-    (void)hipGetLastError();
-    return TQR_ENODEV;
-  }
-  if (strncmp(pr.gcnArchName, "gfx950", 6) != 0) {
-    fprintf(stderr, "tqr: device %d is %s, this build targets gfx950 only\n", dev, pr.gcnArchName);
-    return TQR_ENODEV;
-  }
-  HIPCHK(hipFuncSetAttribute((const void*)pp->kn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS));
-  HIPCHK(hipFuncSetAttribute((const void*)pp->kt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS));
-  HIPCHK(hipFuncSetAttribute((const void*)pp->kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PIPE_LDS));
-  if (!pp->evDone) HIPCHK(hipEventCreateWithFlags(&pp->evDone, hipEventDisableTiming));
-  int* ws = nullptr;
-  if (hipMalloc(&ws, pp->ws_bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return TQR_ENOMEM;
-  }
-  if (hipMemset(ws, 0, pp->ws_bytes) != hipSuccess) {
-    (void)hipFree(ws);
-    return TQR_EHIP;
-  }
-  pp->d_ws = ws;
-  return TQR_OK;
-}
 
 // tqr_apply_pipe_q's argument errors (everything but the handle's prepared state, which needs ap->mu)
 static bool apply_pipe_args_ok(const tqr_apply_pipe* pp, const tqr_apply* ap, int trans, const void* dA, int ldda,
                                const void* dC, int nrhs, int lddc) {
   return pp && ap && dA && dC && (trans == TQR_NOTRANS || trans == TQR_TRANS) && nrhs >= 1 && nrhs <= pp->nrhs_max &&
-         ldda >= pp->m && lddc >= pp->m && apply_valid_ld(ldda, pp->es) && apply_valid_ld(lddc, pp->es) && ap->m == pp->m &&
+         ldda >= pp->m && lddc >= pp->m && valid_ld(ldda, pp->es) && valid_ld(lddc, pp->es) && ap->m == pp->m &&
          ap->n == pp->n && ap->b == pp->b && ap->dtype == pp->dtype;
 }
 
@@ -512,32 +414,24 @@ static bool apply_pipe_args_ok(const tqr_apply_pipe* pp, const tqr_apply* ap, in
 static int apply_pipe_enqueue(tqr_apply_pipe* pp, tqr_apply* ap, apfn kern, unsigned grid, const void* dA, int ldda, void* dC,
                               int nrhs, int lddc, void* stream) {
   hipStream_t cs = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lp(pp->mu);  // (always pp's before ap's)
+  std::lock_guard<std::mutex> lp(pp->core.mu);  // (always pp's before ap's)
   std::lock_guard<std::mutex> la(ap->mu);
   if (!ap->prepared) return TQR_EINVAL;
-  if (const int st = apply_pipe_ready(pp)) return st;
-  HIPCHK(hipStreamWaitEvent(cs, pp->evDone, 0));  // the previous call of this handle (any stream)
-  if (pp->epoch == INT_MAX) {  // the epochs start over: behind the previous call, ahead of this one
-    HIPCHK(hipMemsetAsync(pp->d_ws + PIPE_HDR, 0, pp->ws_bytes - PIPE_HDR * sizeof(int), cs));
-    pp->epoch = 0;
-  }
+  if (const int st = pipe_ready(pp->core)) return st;
+  ApplyPipeArgs a;
+  if (const int st = pipe_call_begin(pp->core, cs, &a.epoch)) return st;
   int slot = 0;
   HIPCHK(apply_enqueue_begin(ap, cs, &slot));
-  ApplyPipeArgs a;
   a.q.A = dA; a.q.tau = nullptr; a.q.C = dC; a.q.Tw = ap->d_T; a.q.lda = ldda; a.q.ldc = lddc;
   a.q.m = pp->m; a.q.p = pp->p; a.q.kmax = pp->kmax; a.q.nrhs = nrhs;
   a.nslot = pp->nslot;
-  a.epoch = pp->epoch + 1;
-  a.ws = pp->d_ws;
-  HIPCHK(hipMemsetAsync(pp->d_ws + PIPE_TICKET, 0, sizeof(int), cs));  // (the error word stays: tqr_apply_pipe_status)
+  a.ws = pp->core.d_ws;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), PIPE_LDS, cs, a);
-  const hipError_t le = hipGetLastError();
-  // recorded behind whatever was enqueued, so the next call and the next prepare stay ordered after it
-  const hipError_t re = hipEventRecord(pp->evDone, cs);
+  // evDone and ap's slot are both recorded whatever the launch did, so the next call and the next
+  // prepare stay ordered after whatever was enqueued
+  const int st = pipe_call_end(pp->core, cs, hipGetLastError(), a.epoch);
   const hipError_t ae = apply_enqueue_end(ap, cs, slot);
-  HIPCHK(le);
-  pp->epoch = a.epoch;  // committed once the launch is enqueued
-  HIPCHK(re);
+  if (st) return st;
   HIPCHK(ae);
   return TQR_OK;
 }
@@ -548,25 +442,21 @@ int tqr_apply_pipe_ticket(int kmax, int nstrips, int trans, int ticket, int* str
   if (kmax < 1 || nstrips < 1 || (trans != TQR_NOTRANS && trans != TQR_TRANS) || !strip || !step || ticket < 0 ||
       (long long)ticket >= (long long)kmax * nstrips)
     return TQR_EINVAL;
-  apply_ticket_map(kmax, nstrips, trans == TQR_TRANS, ticket, strip, step);
+  pipe_ticket_map(kmax, nstrips, trans == TQR_TRANS, ticket, strip, step);
   return TQR_OK;
 }
 
 void tqr_apply_pipe_destroy(tqr_apply_pipe* pp) {
   if (!pp) return;
-  if (pp->evDone) {
-    (void)hipEventSynchronize(pp->evDone);  // the last call may still be reading the workspace
-    (void)hipEventDestroy(pp->evDone);
-  }
-  if (pp->d_ws) (void)hipFree(pp->d_ws);
+  pipe_destroy(pp->core);
   delete pp;
 }
 
 int tqr_apply_pipe_create(tqr_apply_pipe** out, int m, int n, int b, int dtype, int nrhs_max) {
   if (!out) return TQR_EINVAL;
   *out = nullptr;
-  if (!apply_valid_b(b) || m <= 0 || n <= 0 || m % b || n % b || (dtype != TQR_F32 && dtype != TQR_F64) ||
-      !apply_valid_ld(m, dtype == TQR_F64 ? 8 : 4) || nrhs_max < 1)
+  if (!valid_b(b) || m <= 0 || n <= 0 || m % b || n % b || (dtype != TQR_F32 && dtype != TQR_F64) ||
+      !valid_ld(m, elem_size(dtype)) || nrhs_max < 1)
     return TQR_EINVAL;
   const int p = m / b, q = n / b, kmax = p < q ? p : q;
   const size_t nstrips = ((size_t)nrhs_max + 63) / 64, items = nstrips * (size_t)kmax;
@@ -574,15 +464,15 @@ int tqr_apply_pipe_create(tqr_apply_pipe** out, int m, int n, int b, int dtype, 
   tqr_apply_pipe* pp = new (std::nothrow) tqr_apply_pipe();
   if (!pp) return TQR_ENOMEM;
   pp->m = m; pp->n = n; pp->b = b; pp->p = p; pp->kmax = kmax; pp->dtype = dtype; pp->nrhs_max = nrhs_max;
-  pp->es = dtype == TQR_F64 ? 8 : 4;
+  pp->es = elem_size(dtype);
   pp->nslot = (long long)tile_slot(kmax, kmax, p);
-  pp->ws_bytes = ((size_t)PIPE_HDR + nstrips * (size_t)pp->nslot) * sizeof(int);
-  pp->kn = apipe_kernel_b(b, dtype, TQR_NOTRANS);
-  pp->kt = apipe_kernel_b(b, dtype, TQR_TRANS);
-  pp->kf = aform_kernel_b(b, dtype);
+  pp->core.ws_bytes = ((size_t)PIPE_HDR + nstrips * (size_t)pp->nslot) * sizeof(int);
+  pp->core.kern[0] = (const void*)(pp->kn = apipe_kernel_b(b, dtype, TQR_NOTRANS));
+  pp->core.kern[1] = (const void*)(pp->kt = apipe_kernel_b(b, dtype, TQR_TRANS));
+  pp->core.kern[2] = (const void*)(pp->kf = aform_kernel_b(b, dtype));
   // without a gfx950 the handle exists but holds no device memory: every call on it validates its
   // arguments and then returns TQR_ENODEV
-  const int st = apply_pipe_ready(pp);
+  const int st = pipe_ready(pp->core);
   if (st != TQR_OK && st != TQR_ENODEV) {
     tqr_apply_pipe_destroy(pp);
     return st;
@@ -591,7 +481,7 @@ int tqr_apply_pipe_create(tqr_apply_pipe** out, int m, int n, int b, int dtype, 
   return TQR_OK;
 }
 
-size_t tqr_apply_pipe_workspace_bytes(const tqr_apply_pipe* pp) { return pp ? pp->ws_bytes : 0; }
+size_t tqr_apply_pipe_workspace_bytes(const tqr_apply_pipe* pp) { return pp ? pp->core.ws_bytes : 0; }
 
 int tqr_apply_pipe_q(tqr_apply_pipe* pp, tqr_apply* ap, int trans, const void* dA, int ldda, void* dC, int nrhs,
                      int lddc, void* stream) {
@@ -608,31 +498,22 @@ int tqr_apply_pipe_form_q(tqr_apply_pipe* pp, tqr_apply* ap, const void* dA, int
 }
 
 int tqr_apply_pipe_form_q_items(int kmax, int b, int ncols) {
-  if (kmax < 1 || !apply_valid_b(b) || ncols < 1) return TQR_EINVAL;
+  if (kmax < 1 || !valid_b(b) || ncols < 1) return TQR_EINVAL;
   const long long n = form_q_items(kmax, b, ncols);
   return n > 0x7fffffffll ? TQR_EINVAL : (int)n;
 }
 
 int tqr_apply_pipe_form_q_ticket(int kmax, int b, int ncols, int ticket, int* strip, int* step) {
-  if (kmax < 1 || !apply_valid_b(b) || ncols < 1 || !strip || !step || ticket < 0) return TQR_EINVAL;
+  if (kmax < 1 || !valid_b(b) || ncols < 1 || !strip || !step || ticket < 0) return TQR_EINVAL;
   int s, k;
   if (!form_q_ticket_map(kmax, b, ncols, ticket, &s, &k)) return TQR_EINVAL;
   *strip = s;
   *step = k;
   return TQR_OK;
 }
+
 int tqr_apply_pipe_status(tqr_apply_pipe* pp, void* stream) {
-  if (!pp) return TQR_EINVAL;
-  std::lock_guard<std::mutex> lk(pp->mu);
-  if (!pp->d_ws) return TQR_OK;  // nothing was ever enqueued
-  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-  HIPCHK(hipEventSynchronize(pp->evDone));  // the handle's last call, whatever its stream
-  int err = 0;
-  HIPCHK(hipMemcpy(&err, pp->d_ws + PIPE_ERR, sizeof(int), hipMemcpyDeviceToHost));
-  if (!err) return TQR_OK;
-  fprintf(stderr, "tqr: pipelined apply: a wait for another workgroup's row tile timed out (error word %d)\n", err);
-  HIPCHK(hipMemset(pp->d_ws + PIPE_ERR, 0, sizeof(int)));  // reported once; the handle is usable again
-  return TQR_EHIP;
+  return pp ? pipe_status(pp->core, stream, "apply: a wait for another workgroup's row tile") : TQR_EINVAL;
 }
 
 // tqr_lstsq (apply.hip) with the pipelined apply and the pipelined solve in place of tqr_apply_q and

@@ -33,6 +33,7 @@
 
 #include "flowplan.hpp"
 #include "gridscheduler.h"
+#include "host_common.hpp"
 #include "solve.hpp"
 #include "tiles.hpp"
 #include "tqr.h"
@@ -385,10 +386,6 @@ static int resolve(int b, int dtype, kfn* kp, kfn* ku, kfn* kt) {
   return TQR_OK;
 }
 
-// The engine's buffer resources are based at a strip's or reflector group's first column and
-// address at most 32 columns with 32-bit byte offsets (tiles.hpp load_strip_pair, flow.hpp):
-// 32 * ldm * es must stay below 2^31 (ldm <= 8,388,607 rows fp64, 16,777,215 fp32).
-static bool valid_ld(long ld, size_t es) { return ld > 0 && (size_t)32 * (size_t)ld * es <= 0x7fffffffull; }
 // workspace slot sizes (doubles) of Geo<b, ib>::TIMG / VIMG / TPIMG (ib: reflectors per group)
 static size_t timg_doubles(int b, int ib = 32) {
   ib = std::min(b, ib);
@@ -498,15 +495,6 @@ struct XferArgs {
   int gen;
 };
 
-#define HIPCHK(x)                                                                         \
-  do {                                                                                    \
-    hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess) {                                                               \
-      fprintf(stderr, "tqr: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); \
-      return TQR_EHIP;                                                                    \
-    }                                                                                     \
-  } while (0)
-
 extern "C" {
 
 const char* tqr_strerror(int s) {
@@ -526,18 +514,6 @@ const char* tqr_version(void) { return "tqr 0.1 (gfx950, flat-tree tiled Househo
 long tqr_total_tasks(int m, int n, int b) {
   if (b <= 0 || m % b || n % b) return -1;
   return tqr_sched_total_tasks(m / b, n / b);
-}
-
-static int check_device() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return TQR_ENODEV;
-  hipDeviceProp_t pr;
-  if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return TQR_ENODEV;
-  if (strncmp(pr.gcnArchName, "gfx950", 6) != 0) {
-    fprintf(stderr, "tqr: device %d is %s, this build targets gfx950 only\n", dev, pr.gcnArchName);
-    return TQR_ENODEV;
-  }
-  return TQR_OK;
 }
 
 static void close_opened(tqr_plan* pl);
@@ -635,9 +611,9 @@ static int plan_create(tqr_plan** out, int m, int n, int b, int dtype, int rank,
   if (!out) return TQR_EINVAL;
   *out = nullptr;
   if (!valid_b(b) || m <= 0 || n <= 0 || m % b || n % b || (dtype != TQR_F32 && dtype != TQR_F64) ||
-      !valid_ld(m, dtype == TQR_F64 ? 8 : 4))
+      !valid_ld(m, elem_size(dtype)))
     return TQR_EINVAL;
-  int st = check_device();
+  int st = current_device_is_gfx950();
   if (st) return st;
   tqr_plan* pl = new (std::nothrow) tqr_plan();
   if (!pl) return TQR_ENOMEM;
@@ -646,7 +622,7 @@ static int plan_create(tqr_plan** out, int m, int n, int b, int dtype, int rank,
   pl->capped = steps > 0;
   pl->kmax = flow_kmax(pl->p, pl->q, steps);
   pl->dtype = dtype;
-  pl->es = dtype == TQR_F64 ? 8 : 4;
+  pl->es = elem_size(dtype);
 
   tqr_plan_t sp;
   if (tqr_sched_plan(pl->p, pl->q, &sp) != 0) { delete pl; return TQR_ENOMEM; }
@@ -1213,7 +1189,7 @@ static int cached_plan(int m, int n, int b, int dtype, PlanRef& ref, int engine 
 // refuse anyway must not first build (and keep) a plan, nor need a device to be told so.
 static int geqrt_tiled(int m, int n, int b, int dtype, void* dA, int ldda, void* dtau, void* stream) {
   if (!dA || !dtau || !valid_b(b) || m <= 0 || n <= 0 || m % b || n % b || ldda < m ||
-      !valid_ld(ldda, dtype == TQR_F64 ? 8 : 4))
+      !valid_ld(ldda, elem_size(dtype)))
     return TQR_EINVAL;
   PlanRef r;
   int st = cached_plan(m, n, b, dtype, r);
@@ -1584,7 +1560,7 @@ static int geqrt_host(void* A, void* tau, int m, int n, int ldm, int b, int dtyp
   if (st) return st;
   tqr_plan* pl = ref.pl;
   std::lock_guard<std::mutex> lk(pl->hmu);
-  const size_t es = dtype == TQR_F64 ? 8 : 4;
+  const size_t es = elem_size(dtype);
   if (pl->engine == TQR_ENGINE_FLOW) return geqrt_host_flow(pl, A, tau, ldm, es);
   if ((st = plan_host_buffers(pl, es)) || (st = plan_pinned_staging(pl, es))) return st;
   char* dA = (char*)pl->hA;
@@ -1668,9 +1644,9 @@ struct TileRun {
   Item* dit = nullptr;
   kfn kp, ku, kt;
   int init(int b_, int dtype_, int p, int q) {
-    b = b_; dtype = dtype_; mr = p * b; nc = q * b; es = dtype == TQR_F64 ? 8 : 4;
+    b = b_; dtype = dtype_; mr = p * b; nc = q * b; es = elem_size(dtype);
     if (!valid_b(b) || (dtype != TQR_F64 && dtype != TQR_F32)) return TQR_EINVAL;
-    int st = check_device();
+    int st = current_device_is_gfx950();
     if (st) return st;
     if ((st = resolve(b, dtype, &kp, &ku, &kt))) return st;
     int ib = b < 32 ? b : 32;
@@ -1786,12 +1762,12 @@ int tqr_tile_batch(int dtype, int type, int b, int nblocks, const void* V, int l
   const int rows = type == DAPP ? 2 * b : b;  // rows of one block: [A; B] or C
   if (ldv < b || ldb < rows || (out && ldo < rows)) return TQR_EINVAL;
   // the batch lives in one 2b-row device matrix addressed by 32-bit buffer offsets
-  if ((size_t)(dtype == TQR_F64 ? 8 : 4) * 2 * b * ((size_t)(1 + nblocks) * b) > 0x7fffffffull) return TQR_EINVAL;
-  int st = check_device();
+  if (elem_size(dtype) * 2 * b * ((size_t)(1 + nblocks) * b) > 0x7fffffffull) return TQR_EINVAL;
+  int st = current_device_is_gfx950();
   if (st) return st;
   kfn kp, ku, kt;
   if ((st = resolve(b, dtype, &kp, &ku, &kt))) return st;
-  const size_t es = dtype == TQR_F64 ? 8 : 4;
+  const size_t es = elem_size(dtype);
   const int mr = 2 * b, ng = b / (b < 32 ? b : 32), nstrips = (b + 63) / 64;
   const size_t nc = (size_t)(1 + nblocks) * b;
   void *dA = nullptr, *dtau = nullptr;

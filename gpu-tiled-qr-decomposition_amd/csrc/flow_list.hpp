@@ -17,6 +17,9 @@ struct Item {
   int ts, l, m, k;
 };
 
+// the tile sizes the library is built for (every create and one-shot call checks its b with this)
+inline bool valid_b(int b) { return b == 16 || b == 32 || b == 64 || b == 128 || b == 256; }
+
 constexpr int T_CHAIN = 4;
 constexpr int T_UP = 5, T_DOWN = 6;  // host <-> HBM transfer tasks (xfer.hpp)
 

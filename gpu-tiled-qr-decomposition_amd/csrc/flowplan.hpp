@@ -11,8 +11,6 @@
 
 namespace tqr {
 
-inline bool valid_b(int b) { return b == 16 || b == 32 || b == 64 || b == 128 || b == 256; }
-
 // Engine shape of the persistent kernel (flow_list.hpp FlowShape): 8 = ShapeW8 (one 8-wave workgroup per
 // CU, 128-column strips, 32-reflector groups; the default), 4 = ShapeW4 (two 4-wave workgroups per
 // CU, 64-column strips, 16-reflector groups; fp64 with TQR_FLOW_SHAPE=w4)

@@ -17,9 +17,7 @@
 // so the rows a step stores and a later step reloads are ordered by program order.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstring>
-
+#include "host_common.hpp"
 #include "solve.hpp"
 #include "solve_dev.hpp"
 #include "tqr.h"
@@ -157,29 +155,11 @@ static sfn solve_kernel(int dtype, int trans) {
   if (dtype == TQR_F64) return trans == TQR_TRANS ? k_trsm_r<B, double, true> : k_trsm_r<B, double, false>;
   return trans == TQR_TRANS ? k_trsm_r<B, float, true> : k_trsm_r<B, float, false>;
 }
-// (lds_solve, solve_valid_b, solve_valid_ld: solve_dev.hpp)
-
-#define HIPCHK(x)                                                                         \
-  do {                                                                                    \
-    hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess) {                                                               \
-      fprintf(stderr, "tqr: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); \
-      return TQR_EHIP;                                                                    \
-    }                                                                                     \
-  } while (0)
+// (lds_solve: solve_dev.hpp)
 
 // the current device is a gfx950, and the kernel may use its dynamic LDS (host-side calls only)
 static int solve_ready(sfn fn, size_t ldsz) {
-  int dev = 0;
-  hipDeviceProp_t pr;
-  if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess) {
-    (void)hipGetLastError();
-    return TQR_ENODEV;
-  }
-  if (strncmp(pr.gcnArchName, "gfx950", 6) != 0) {
-    fprintf(stderr, "tqr: device %d is %s, this build targets gfx950 only\n", dev, pr.gcnArchName);
-    return TQR_ENODEV;
-  }
+  if (const int st = current_device_is_gfx950()) return st;
   HIPCHK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsz));
   return TQR_OK;
 }
@@ -201,19 +181,12 @@ using namespace tqr;
 extern "C" {
 
 int tqr_trsm_r(int dtype, int trans, int n, int b, const void* dA, int ldda, void* dX, int nrhs, int lddx, void* stream) {
-  if ((dtype != TQR_F32 && dtype != TQR_F64) || (trans != TQR_NOTRANS && trans != TQR_TRANS) || !solve_valid_b(b) || n <= 0 ||
+  if ((dtype != TQR_F32 && dtype != TQR_F64) || (trans != TQR_NOTRANS && trans != TQR_TRANS) || !valid_b(b) || n <= 0 ||
       n % b || nrhs < 1 || !dA || !dX || ldda < n || lddx < n)
     return TQR_EINVAL;
-  const size_t es = dtype == TQR_F64 ? 8 : 4;
-  if (!solve_valid_ld(ldda, es) || !solve_valid_ld(lddx, es)) return TQR_EINVAL;
-  sfn fn = nullptr;
-  switch (b) {
-    case 16: fn = solve_kernel<16>(dtype, trans); break;
-    case 32: fn = solve_kernel<32>(dtype, trans); break;
-    case 64: fn = solve_kernel<64>(dtype, trans); break;
-    case 128: fn = solve_kernel<128>(dtype, trans); break;
-    default: fn = solve_kernel<256>(dtype, trans); break;
-  }
+  const size_t es = elem_size(dtype);
+  if (!valid_ld(ldda, es) || !valid_ld(lddx, es)) return TQR_EINVAL;
+  const sfn fn = dispatch_b(b, [&](auto bb) { return solve_kernel<decltype(bb)::value>(dtype, trans); });
   const int st = solve_ready(fn, lds_solve(b));
   if (st != TQR_OK) return st;
   SolveArgs a;
@@ -232,9 +205,9 @@ int tqr_lstsq_fused(tqr_plan* plan, void* dAB, int ldda, void* dtau, int nrhs, v
   const PlanShape ps = plan_shape(plan);
   const int n = ps.steps * ps.b;  // A's columns; B's tile columns follow
   if (!ps.capped || n >= ps.n || ps.m < n || nrhs < 1 || nrhs > ps.n - n || ldda < ps.m ||
-      !solve_valid_ld(ldda, ps.dtype == TQR_F64 ? 8 : 4))
+      !valid_ld(ldda, elem_size(ps.dtype)))
     return TQR_EINVAL;
-  void* dB = (char*)dAB + (size_t)n * (size_t)ldda * (ps.dtype == TQR_F64 ? 8 : 4);
+  void* dB = (char*)dAB + (size_t)n * (size_t)ldda * elem_size(ps.dtype);
   int st;
   if ((st = tqr_plan_execute(plan, dAB, ldda, dtau, stream)) != TQR_OK) return st;
   if ((st = tqr_trsm_r(ps.dtype, TQR_NOTRANS, n, ps.b, dAB, ldda, dB, nrhs, ldda, stream)) != TQR_OK) return st;

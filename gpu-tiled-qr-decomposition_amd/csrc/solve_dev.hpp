@@ -145,12 +145,9 @@ __device__ __forceinline__ void load_x(double (&X)[Geo<B>::NKS], __amdgpu_buffer
   }
 }
 
-// ---- host side, shared by the two units' argument checks ----------------------------------------
+// ---- host side, shared by the two units' launches -----------------------------------------------
 // dynamic LDS (bytes): one operand image, b x (IB + 2) doubles (Geo<b>::VSZ)
 static inline size_t lds_solve(int b) { return (size_t)b * ((b < 32 ? b : 32) + 2) * sizeof(double); }
 static_assert(Geo<256>::VSZ * sizeof(double) == 69632 && Geo<16>::VSZ == 16 * 18, "host lds_solve mirrors Geo::VSZ");
-static inline bool solve_valid_b(int b) { return b == 16 || b == 32 || b == 64 || b == 128 || b == 256; }
-// the library's leading-dimension bound (include/tqr.h): 32 * ld * sizeof(element) < 2^31
-static inline bool solve_valid_ld(long ld, size_t es) { return ld > 0 && (size_t)32 * (size_t)ld * es <= 0x7fffffffull; }
 
 }  // namespace tqr

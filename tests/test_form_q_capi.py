@@ -10,7 +10,7 @@ the ap of these calls is a pointer that validation never reaches — ap is looke
 which is itself the error. What needs a real ap — an ap of another shape, an unprepared ap, and each
 refusal once more against a prepared one — is in tests/test_gpu_form_q.py. TQR_ENODEV for a valid
 call on a handle without a device would need a prepared ap on a machine without a device, which
-cannot exist: that path (apply_pipe_ready, shared with tqr_apply_pipe_q) is read in the code."""
+cannot exist: that path (pipe_ready, shared with tqr_apply_pipe_q) is read in the code."""
 import ctypes
 
 import pytest

@@ -162,3 +162,14 @@ def test_ticket_invalid_args(tqr):
     # a product that overflows int is still judged in 64 bits
     assert L.tqr_solve_ticket(2 ** 20, 2 ** 20, 0, 2 ** 31 - 1, ctypes.byref(s), ctypes.byref(r)) == 0
     assert (s.value, r.value) == ((2 ** 31 - 1) % 2 ** 20, 2 ** 20 - 1 - (2 ** 31 - 1) // 2 ** 20)
+
+
+@pytest.mark.parametrize("n, ns, trans, t", [(1, 1, 0, 0), (4, 1, 0, 3), (4, 3, 1, 7), (9, 5, 0, 44), (9, 5, 1, 0),
+                                             (2 ** 20, 2 ** 20, 0, 2 ** 31 - 1), (2 ** 20, 2 ** 20, 1, 2 ** 31 - 1)])
+def test_ticket_map_shared_with_the_pipelined_apply(tqr, n, ns, trans, t):
+    """tqr_solve_ticket and tqr_apply_pipe_ticket evaluate one map: the same (strip, position)."""
+    L = tqr.lib()
+    s, k = ctypes.c_int(-7), ctypes.c_int(-7)
+    assert L.tqr_apply_pipe_ticket(n, ns, trans, t, ctypes.byref(s), ctypes.byref(k)) == 0
+    assert ticket(L, n, ns, trans, t) == (0, s.value, k.value)
+    assert (s.value, k.value) == (t % ns, t // ns if trans else n - 1 - t // ns)
