@@ -696,7 +696,7 @@ static int plan_create(tqr_plan** out, int m, int n, int b, int dtype, int rank,
     pl->grid = full_grid;
     if (const char* gs = getenv("TQR_FLOW_GRID")) pl->grid = std::max(1, atoi(gs));
     FlowPlan fp;
-    pl->knobs = flow_knobs(pl->p, pl->q, dtype, world, pl->grid >= full_grid, 0, steps);
+    pl->knobs = flow_knobs(pl->p, pl->q, dtype, world, pl->grid >= full_grid, 0, steps, b);
     if (const char* eca = getenv("TQR_CHAIN_ASM")) pl->chain_asm = atoi(eca) & 3;  // 0 off, 1 on, 2 late strip loads
     // (bit 2: UNMQR elements on the full TSMQR bodies instead of the zero-row-skipping ones; A/B only)
     if (const char* eu = getenv("TQR_UNMQR_SKIP"); eu && atoi(eu) == 0 && pl->chain_asm) pl->chain_asm |= 4;
@@ -991,6 +991,21 @@ int tqr_plan_set_tasks(tqr_plan* pl, const int* items, int n) {
   if (ka != kb || !flow_list_topological(L, pl->p, pl->q, pl->ns)) return TQR_EINVAL;
   HIPCHK(hipMemcpy(pl->d_flow, L.data(), sizeof(Item) * n, hipMemcpyHostToDevice));
   return TQR_OK;
+}
+
+int tqr_plan_get_tasks(tqr_plan* pl, int* items, int cap) {
+  if (!pl || pl->engine != TQR_ENGINE_FLOW || cap < 0 || (cap > 0 && !items)) return TQR_EINVAL;
+  const int n = std::min(cap, pl->nflow);
+  if (n > 0) {
+    std::vector<Item> cur(n);
+    std::lock_guard<std::mutex> lk(pl->mu);
+    HIPCHK(hipMemcpy(cur.data(), pl->d_flow, sizeof(Item) * n, hipMemcpyDeviceToHost));
+    for (int x = 0; x < n; ++x) {
+      items[4 * x] = cur[x].ts; items[4 * x + 1] = cur[x].l;
+      items[4 * x + 2] = cur[x].m; items[4 * x + 3] = cur[x].k;
+    }
+  }
+  return pl->nflow;
 }
 
 int tqr_plan_debug_workspace(const tqr_plan* pl, int k, void* host, size_t bytes) {

@@ -5,9 +5,12 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
+#include <queue>
 #include <string>
 #include <tuple>
+#include <unordered_map>
 
 #include "gridscheduler.h"
 
@@ -31,10 +34,20 @@ int flow_shape(int dtype, int b) {
 // Host-pointer API lists (xfer.hpp) also hold UP(j, c) / DOWN(j, c): every step-0 task of tile
 // column j (GEQRT(0) / TSQRT(i, 0) for j = 0, the chains of step 0 on j) must come after all
 // UP(j, *); DOWN(j, c) after every chain of a step k < j on column j and every panel task of step j.
+// (the positions are kept in hash maps under packed keys: k, s, e and the rows of a chain are 16-bit
+// or narrower fields of the task word, a panel's row is any int, and steps and tile columns are
+// checked against q <= 65536)
+namespace {
+using u64 = unsigned long long;
+inline u64 key_panel(int i, int k) { return (u64)(unsigned)i << 24 | (u64)k; }                                      // k < q
+inline u64 key_chain(int k, int j, int s, int x) { return (u64)k << 48 | (u64)j << 24 | (u64)s << 16 | (u64)(x & 0xffff); }  // x: e or row
+}  // namespace
 bool flow_list_topological(const std::vector<Item>& L, int p, int q, int ns) {
-  std::map<std::pair<int, int>, int> ppos;                       // (i, k) -> position
-  std::map<std::tuple<int, int, int, int>, int> cpos;            // (k, j, s, e) -> position
-  std::map<std::tuple<int, int, int, int>, int> rowpos;          // (k, j, s, row) -> position
+  if (q > (1 << 16)) return false;  // (a chain's step is a 16-bit field: no list of a wider grid exists)
+  std::unordered_map<u64, int> ppos, cpos, rowpos;               // (i, k) / (k, j, s, e) / (k, j, s, row) -> position
+  ppos.reserve(L.size());
+  cpos.reserve(L.size());
+  rowpos.reserve(4 * L.size());
   std::map<std::pair<int, int>, int> upos, dpos;                 // (j, c) -> position
   std::vector<int> uplast(q, -1);                                // last UP(j, *) of column j
   std::vector<int> collast(q, -1);                               // last task DOWN(j, *) waits for
@@ -44,13 +57,13 @@ bool flow_list_topological(const std::vector<Item>& L, int p, int q, int ns) {
     if (ty == T_CHAIN) {
       const int s = (it.ts >> 8) & 0xff, k = it.k & 0xffff, e = it.k >> 16, j = it.m, i0 = it.l & 0xffff, i1 = it.l >> 16;
       if (j < 0 || j >= q) return false;
-      if (!cpos.emplace(std::make_tuple(k, j, s, e), x).second) return false;
-      if (e == 0) rowpos[std::make_tuple(k, j, s, k)] = x;
-      for (int i = i0; i < i1; ++i) rowpos[std::make_tuple(k, j, s, i)] = x;
+      if (!cpos.emplace(key_chain(k, j, s, e), x).second) return false;
+      if (e == 0) rowpos[key_chain(k, j, s, k)] = x;
+      for (int i = i0; i < i1; ++i) rowpos[key_chain(k, j, s, i)] = x;
       if (k < j) collast[j] = std::max(collast[j], x);
     } else if (ty == QRS || ty == QRD) {
       if (it.k < 0 || it.k >= q) return false;
-      if (!ppos.emplace(std::make_pair(it.l, it.k), x).second) return false;
+      if (!ppos.emplace(key_panel(it.l, it.k), x).second) return false;
       collast[it.k] = std::max(collast[it.k], x);
     } else if (ty == T_UP || ty == T_DOWN) {
       if (it.m < 0 || it.m >= q) return false;
@@ -80,23 +93,23 @@ bool flow_list_topological(const std::vector<Item>& L, int p, int q, int ns) {
     const int ty = it.ts & 0xff;
     if (ty == T_CHAIN) {
       const int s = (it.ts >> 8) & 0xff, k = it.k & 0xffff, e = it.k >> 16, j = it.m, i0 = it.l & 0xffff, i1 = it.l >> 16;
-      if (e > 0 && !before(cpos, std::make_tuple(k, j, s, e - 1), x)) return false;
-      if (e == 0 && !before(ppos, std::make_pair(k, k), x)) return false;
-      if (e == 0 && k > 0 && !before(rowpos, std::make_tuple(k - 1, j, s, k), x)) return false;
+      if (e > 0 && !before(cpos, key_chain(k, j, s, e - 1), x)) return false;
+      if (e == 0 && !before(ppos, key_panel(k, k), x)) return false;
+      if (e == 0 && k > 0 && !before(rowpos, key_chain(k - 1, j, s, k), x)) return false;
       if (xfer && k == 0 && !(uplast[j] < x)) return false;
       for (int i = i0; i < i1; ++i) {
-        if (!before(ppos, std::make_pair(i, k), x)) return false;
-        if (k > 0 && !before(rowpos, std::make_tuple(k - 1, j, s, i), x)) return false;
+        if (!before(ppos, key_panel(i, k), x)) return false;
+        if (k > 0 && !before(rowpos, key_chain(k - 1, j, s, i), x)) return false;
       }
     } else if (ty == T_DOWN) {
       if (!(collast[it.m] < x)) return false;
     } else if (ty == QRS || ty == QRD) {
       const int i = it.l, k = it.k;
-      if (i > k && !before(ppos, std::make_pair(i - 1, k), x)) return false;
+      if (i > k && !before(ppos, key_panel(i - 1, k), x)) return false;
       if (xfer && k == 0 && !(uplast[0] < x)) return false;
       if (k > 0)
         for (int s = 0; s < ns; ++s)
-          if (!before(rowpos, std::make_tuple(k - 1, k, s, i), x)) return false;
+          if (!before(rowpos, key_chain(k - 1, k, s, i), x)) return false;
     }
   }
   (void)p;
@@ -169,6 +182,23 @@ static FlowKnobs knobs_from_env(int seglen, int tail_default, double la_default,
   if (const char* elac = getenv("TQR_LAC")) kn.lac = atof(elac);  // lookahead column's chains (default: TQR_LA)
   return kn;
 }
+// Default window of the deep-lookahead order (window_order; TQR_DEPTH) by the plan's steps: a quarter
+// of the steps plus 4, kept below the number of steps that precede the one-element tail, and only for
+// 44 to 80 steps of a matrix that is not taller than wide (its last `tail` = kTailRows + 1 steps are
+// the latency-bound ones the window is for). Measured on one MI355X, fp64, b = 256, alternating
+// against depth 0, best of the depths tried in ms (profiles/window/depth_by_size.md): 44 steps -2.3
+// at depth 11 (15: -0.5), 48 -3.2 at 16, 56 -3.9 at 18, 64 -3.6 at 20, 72 -3.1 at 22, 80 -1.3 at 24
+// (of 219); 40 steps -0.7 at 6 and nothing at 12-14, 88 -1.0 at 22 and -0.5 at 26 (within the runs'
+// spread), 96 nothing at 8-32. The model (tools/sched_sim.py window) has its best depth at 16-24 for
+// 64 steps and predicts the gain at 44-72 steps, but also -3 ms at 80-96 steps, which the hardware
+// does not give: the upper limit is the measured one. Taller than wide loses in both (96x64 tiles:
+// +3.4 ms, model +0.6; 256x64: +26 ms): such a run has no latency-bound tail to hide, and the
+// window only takes the bulk's workgroups early.
+constexpr int kDepthMinSteps = 44, kDepthMaxSteps = 80;
+static int default_depth(int kmax, int tail) {
+  if (kmax < kDepthMinSteps || kmax > kDepthMaxSteps || tail != kTailRows + 1) return 0;
+  return std::min(kmax / 4 + 4, kmax - tail - 1);
+}
 // Chain segment length (elements per chain task; TQR_SEGLEN overrides). 8, except for 4 and more
 // ranks with a whole device each (1024+ workgroups in all): 2 — more, shorter chain tasks give
 // each rank work it can start while its columns' wavefronts (the head rows going down a column)
@@ -182,9 +212,19 @@ static int env_seglen(int world, bool full) {
   const char* sl = getenv("TQR_SEGLEN");
   return sl ? std::max(1, atoi(sl)) : (world >= 4 && full ? 2 : 8);
 }
-FlowKnobs flow_knobs(int p, int q, int dtype, int world, bool full, int seglen, int steps) {
-  const MultiRankDefaults mrd = multi_rank_defaults(p, flow_kmax(p, q, steps), dtype, world, full);
-  return knobs_from_env(seglen > 0 ? seglen : env_seglen(world, full), mrd.tail, default_la(dtype), mrd.lac, mrd.ualone);
+FlowKnobs flow_knobs(int p, int q, int dtype, int world, bool full, int seglen, int steps, int b) {
+  const int kmax = flow_kmax(p, q, steps);
+  const MultiRankDefaults mrd = multi_rank_defaults(p, kmax, dtype, world, full);
+  FlowKnobs kn = knobs_from_env(seglen > 0 ? seglen : env_seglen(world, full), mrd.tail, default_la(dtype), mrd.lac, mrd.ualone);
+  // the deep-lookahead default: only where window_order's costs were measured — one rank on a whole
+  // device, fp64 storage, the 8-wave shape at b = 256 (8 groups, 2 strips), 8-element segments, no
+  // step cap (the host-pointer list never takes the pass: build_flow_plan); TQR_DEPTH forces any
+  // one-rank device list
+  const bool measured = world == 1 && full && dtype == TQR_F64 && b == 256 && flow_shape(dtype, b) == 8 && kn.seglen == 8 &&
+                        (steps <= 0 || steps >= std::min(p, q));  // (a cap at every step is tqr_plan_create's list, tqr.h)
+  kn.depth = measured ? default_depth(kmax, kn.tail) : 0;
+  if (const char* ed = getenv("TQR_DEPTH"); ed && world == 1) kn.depth = std::max(0, atoi(ed));
+  return kn;
 }
 
 void build_flow_plan(int p, int q, int ns, int ng, const FlowKnobs& kn, FlowPlan& fp, const XferPlan* xp, int steps) {
@@ -334,6 +374,226 @@ void build_flow_plan(int p, int q, int ns, int ng, const FlowKnobs& kn, FlowPlan
     fp.items.clear();
     for (auto& t : tl) fp.items.push_back(t.it);
   }
+  if (kn.depth > 0 && !xfer) window_order(fp.items, p, q, ns, ng, kn.depth);
+}
+
+// ---------------------------------------------------------------------------------------
+// Deep-lookahead order (FlowKnobs::depth): list scheduling of the plan's own
+// tasks, segments as they are, against a timing model of the engine on kWinW workgroups — the C++
+// form of tools/sched_sim.py greedy_order(prio="window"), which it reproduces item for item.
+// Each next list slot goes to the workgroup that frees first. A task is eligible once every task
+// it waits on is in the list. Among the eligible tasks whose first useful work could start by
+// then, the best class key wins:
+//   panel (i, k)                    (0, k, i)
+//   chain (k, j, s, e), j <= k + D  (1, j, k, e, s)   the columns left of the window first
+//   every other chain               (2, k, j, e, s)   step-major bulk
+// else the task that can start soonest. The estimator's order above ties the panel front to the
+// bulk (with 256 workgroups it comes out step-major, only column k+1 favoured); here the panels
+// and the chains that feed the next D panels overtake the bulk, so the late, latency-bound panels
+// are done while the bulk still fills the machine. The times follow the engine's waits as
+// sched_sim.py simulate() does (panel members per reflector group through Rr / Rc / Rt; chain
+// elements per group behind the NEXT group's images, Tc of the tile's previous step, Ac of the
+// previous segment's head rows). The planner has no device: the costs are constants, in us,
+// measured at 16384^2 fp64, b = 256, ShapeW8 (profiles/r06/stamps/; tools/sched_sim.py P6).
+// ---------------------------------------------------------------------------------------
+namespace {
+constexpr int kWinW = 256;         // workgroups: one per CU of an MI355X
+// per panel reflector group (flowstamps_f64.txt, "per panel group"): panel_factor 28.45, build_t
+// 10.29, trailing 15.88, panel I/O 12.03 in all — block in, R / V write-back, V/T images out
+constexpr double kWinF = 28.5, kWinBt = 10.3, kWinT = 15.9;
+constexpr double kWinIoIn = 4.0, kWinIoWb = 4.0, kWinIoImg = 4.0;
+// per chain element (timeline_f64.txt): a reflector group of the asm chain body, the
+// late strip load in the element's first group, the strip store in its hand-over group
+constexpr double kWinC = 16.3, kWinELd = 5.0, kWinESt = 6.0;
+constexpr double kWinDisp = 1.5;  // task dequeue (as tools/sched_sim.py P)
+
+struct MinHeapD {
+  std::vector<double> h;
+  void push(double v) { h.push_back(v); std::push_heap(h.begin(), h.end(), std::greater<double>()); }
+  double pop() { std::pop_heap(h.begin(), h.end(), std::greater<double>()); const double v = h.back(); h.pop_back(); return v; }
+  double top() const { return h.front(); }
+};
+}  // namespace
+
+void window_order(std::vector<Item>& L, int p, int q, int ns, int ng, int depth) {
+  const int n = (int)L.size(), NG = std::max(1, ng);
+  if (n == 0 || depth <= 0) return;
+  int kmax = 0;
+  for (const Item& it : L) {
+    const int ty = it.ts & 0xff;
+    if (ty != T_CHAIN && ty != QRS && ty != QRD) return;  // (transfer tasks: not modelled)
+    kmax = std::max(kmax, (ty == T_CHAIN ? it.k & 0xffff : it.k) + 1);
+  }
+  struct Tk { int chain, i, k, j, s, e, i0, i1; };
+  std::vector<Tk> tk(n);
+  // panel (i, k) -> task; chain row (k, j, s, i) -> the task of the segment holding it
+  std::vector<int> ptask((size_t)kmax * p, -1), rowtask((size_t)kmax * q * ns * p, -1);
+  auto rt = [&](int k, int j, int s, int i) -> int& { return rowtask[(((size_t)k * q + j) * ns + s) * p + i]; };
+  for (int x = 0; x < n; ++x) {
+    const Item& it = L[x];
+    if ((it.ts & 0xff) == T_CHAIN) {
+      Tk t{1, 0, it.k & 0xffff, it.m, (it.ts >> 8) & 0xff, it.k >> 16, it.l & 0xffff, it.l >> 16};
+      if (t.j < 0 || t.j >= q || t.s >= ns || t.i1 > p || t.i0 > t.i1 || t.i0 <= t.k || (t.e > 0 && t.i0 == t.i1)) return;
+      for (int i = t.i0; i < t.i1; ++i) rt(t.k, t.j, t.s, i) = x;
+      if (t.e == 0) rt(t.k, t.j, t.s, t.k) = x;  // (the UNMQR row)
+      tk[x] = t;
+    } else {
+      if (it.l < 0 || it.l >= p || it.k < 0 || it.k >= kmax) return;
+      ptask[(size_t)it.k * p + it.l] = x;
+      tk[x] = Tk{0, it.l, it.k, it.k, 0, 0, 0, 0};
+    }
+  }
+  // segment e - 1 of a chain task's segment e > 0: the one holding the row above its first
+  std::vector<int> prevseg(n, -1);
+  for (int x = 0; x < n; ++x) {
+    const Tk& t = tk[x];
+    if (!t.chain || t.e == 0) continue;
+    const int pv = rt(t.k, t.j, t.s, t.i0 - 1);
+    if (pv < 0 || tk[pv].e != t.e - 1) return;
+    prevseg[x] = pv;
+  }
+  // wait targets of task x, without repeats; false: one is not in the list (keep the list)
+  std::vector<int> dbuf;
+  auto deps_of = [&](int x) {
+    dbuf.clear();
+    const Tk& t = tk[x];
+    bool ok = true;
+    auto add = [&](int d) { if (d < 0) ok = false; else dbuf.push_back(d); };
+    if (!t.chain) {
+      if (t.i > t.k) add(ptask[(size_t)t.k * p + t.i - 1]);
+      if (t.k > 0)
+        for (int s = 0; s < ns; ++s) add(rt(t.k - 1, t.k, s, t.i));
+    } else {
+      if (t.e == 0) {
+        add(ptask[(size_t)t.k * p + t.k]);
+        if (t.k > 0) add(rt(t.k - 1, t.j, t.s, t.k));
+      } else {
+        add(prevseg[x]);
+      }
+      for (int i = t.i0; i < t.i1; ++i) {
+        add(ptask[(size_t)t.k * p + i]);
+        if (t.k > 0) add(rt(t.k - 1, t.j, t.s, i));
+      }
+    }
+    std::sort(dbuf.begin(), dbuf.end());
+    dbuf.erase(std::unique(dbuf.begin(), dbuf.end()), dbuf.end());
+    return ok;
+  };
+  std::vector<int> ndep(n), soff(n + 1, 0), succ;
+  for (int x = 0; x < n; ++x) {
+    if (!deps_of(x)) return;
+    ndep[x] = (int)dbuf.size();
+    for (int d : dbuf) ++soff[d + 1];
+  }
+  for (int x = 0; x < n; ++x) soff[x + 1] += soff[x];
+  succ.resize(soff[n]);
+  {
+    std::vector<int> fill(soff.begin(), soff.end() - 1);
+    for (int x = 0; x < n; ++x) {  // (in list order: a task's successors are released in that order)
+      deps_of(x);
+      for (int d : dbuf) succ[fill[d]++] = x;
+    }
+  }
+  // model state: per panel and group Rr (R row published), Rc (images published), E (trailing
+  // update done); Tc per tile strip (its element of the latest step done: the next step's task on
+  // that tile is its only reader, and the one that overwrites it); per chain task the group ends of
+  // its last element (the head rows the next segment waits for)
+  std::vector<double> Rr((size_t)kmax * p * NG), Rc(Rr.size()), E(Rr.size()), Tc((size_t)p * q * ns, 0.0), G((size_t)n * NG, 0.0);
+  auto pg = [&](int i, int k) { return ((size_t)k * p + i) * NG; };
+  auto tc = [&](int i, int j, int s) -> double& { return Tc[((size_t)i * q + j) * ns + s]; };
+  const int g1 = std::min(1, NG - 1);
+  auto ready_time = [&](int x) {
+    const Tk& t = tk[x];
+    double r = 0.0;
+    if (!t.chain) {
+      if (t.k > 0)
+        for (int s = 0; s < ns; ++s) r = std::max(r, tc(t.i, t.k, s));
+      if (t.i > t.k) r = std::max(r, Rr[pg(t.i - 1, t.k)] - kWinIoIn - kWinF - kWinIoWb);
+      return r;
+    }
+    const int i = t.e == 0 ? t.k : t.i0;
+    r = std::max(Rc[pg(i, t.k)], Rc[pg(i, t.k) + g1]);
+    if (t.k > 0) r = std::max(r, tc(i, t.j, t.s));
+    if (t.e > 0) r = std::max(r, G[(size_t)prevseg[x] * NG + g1]);
+    return r;
+  };
+  auto prio_key = [&](int x) -> unsigned long long {
+    const Tk& t = tk[x];
+    auto key = [](unsigned long long c, int a, int b, int e, int s) {
+      return c << 56 | (unsigned long long)a << 40 | (unsigned long long)b << 24 | (unsigned long long)(e & 0xffff) << 8 | (unsigned)(s & 0xff);
+    };
+    if (!t.chain) return key(0, t.k, t.i, 0, 0);
+    return t.j <= t.k + depth ? key(1, t.j, t.k, t.e, t.s) : key(2, t.k, t.j, t.e, t.s);
+  };
+  // place task x on a workgroup free at t0: the engine's timing rules (sched_sim.py simulate)
+  auto place = [&](int x, double t0) {
+    const Tk& t = tk[x];
+    if (!t.chain) {
+      double tt = t0;
+      if (t.k > 0)
+        for (int s = 0; s < ns; ++s) tt = std::max(tt, tc(t.i, t.k, s));
+      const bool prev = t.i > t.k;
+      const size_t me = pg(t.i, t.k), pv = prev ? pg(t.i - 1, t.k) : 0;
+      for (int g = 0; g < NG; ++g) {
+        double gs = g == 0 ? tt : E[me + g - 1];
+        if (prev) gs = std::max(gs, Rr[pv + g]);
+        Rr[me + g] = gs + kWinIoIn + kWinF + kWinIoWb;
+        Rc[me + g] = Rr[me + g] + kWinBt + kWinIoImg;
+        E[me + g] = (prev ? std::max(Rc[me + g], E[pv + g]) : Rc[me + g]) + kWinT;
+      }
+      return E[me + NG - 1];
+    }
+    double tt = t0;
+    const double* hg = t.e > 0 ? &G[(size_t)prevseg[x] * NG] : nullptr;
+    double* last = &G[(size_t)x * NG];
+    const int nrows = (t.e == 0 ? 1 : 0) + (t.i1 - t.i0);
+    auto row = [&](int idx) { return t.e == 0 ? (idx == 0 ? t.k : t.i0 + idx - 1) : t.i0 + idx; };
+    for (int idx = 0; idx < nrows; ++idx) {
+      const int i = row(idx);
+      if (t.k > 0) tt = std::max(tt, tc(i, t.j, t.s));
+      tt += kWinELd;
+      const double* rc = &Rc[pg(i, t.k)];
+      const double nxt = idx + 1 < nrows ? Rc[pg(row(idx + 1), t.k)] : 0.0;
+      for (int g = 0; g < NG; ++g) {
+        const double need = g + 1 < NG ? rc[g + 1] : nxt;
+        double st = std::max({tt, rc[g], need});
+        if (hg && idx == 0) st = std::max(st, hg[std::min(g + 1, NG - 1)]);
+        tt = st + kWinC;
+        last[g] = tt;
+      }
+      tt += kWinESt;
+      tc(i, t.j, t.s) = tt;
+    }
+    return tt;
+  };
+  using NR = std::tuple<double, int, int>;             // (ready time, push count, task)
+  using RD = std::pair<unsigned long long, int>;       // (class key, task): keys are unique
+  std::priority_queue<NR, std::vector<NR>, std::greater<NR>> notready;
+  std::priority_queue<RD, std::vector<RD>, std::greater<RD>> ready;
+  MinHeapD workers;
+  for (int w = 0; w < kWinW; ++w) workers.push(0.0);
+  int cnt = 0;
+  for (int x = 0; x < n; ++x)
+    if (ndep[x] == 0) notready.emplace(ready_time(x), ++cnt, x);
+  std::vector<Item> out;
+  out.reserve(n);
+  while (!notready.empty() || !ready.empty()) {
+    const double tw = workers.top() + kWinDisp;
+    while (!notready.empty() && std::get<0>(notready.top()) <= tw) {
+      const int x = std::get<2>(notready.top());
+      notready.pop();
+      ready.emplace(prio_key(x), x);
+    }
+    int x;
+    if (!ready.empty()) { x = ready.top().second; ready.pop(); }
+    else { x = std::get<2>(notready.top()); notready.pop(); }
+    out.push_back(L[x]);
+    workers.push(place(x, workers.pop() + kWinDisp));
+    for (int u = soff[x]; u < soff[x + 1]; ++u)
+      if (--ndep[succ[u]] == 0) notready.emplace(ready_time(succ[u]), ++cnt, succ[u]);
+  }
+  // (a cycle or a lost task cannot pass: the list must hold every task once, in a topological order)
+  if ((int)out.size() == n && flow_list_topological(out, p, q, ns)) L.swap(out);
 }
 // Multi-GPU: keep this rank's share of the global (topological) order — panel tasks of the tile
 // columns it owns (column k on rank tile_owner(k, world); each forwards its images to the peers itself) and
@@ -377,7 +637,7 @@ int flow_list(const tqr_flow_list_spec& sp, FlowPlan& fp, int steps) {
   xp.nxc = sp.nxc;
   xp.tcol = sp.tcol;
   build_flow_plan(sp.M, sp.N, shape_ns(sh, sp.b), sp.b / shape_ib(sh, sp.b),
-                  flow_knobs(sp.M, sp.N, sp.dtype, sp.world, sp.full != 0, sp.seglen, steps), fp, sp.nxc > 0 ? &xp : nullptr, steps);
+                  flow_knobs(sp.M, sp.N, sp.dtype, sp.world, sp.full != 0, sp.seglen, steps, sp.b), fp, sp.nxc > 0 ? &xp : nullptr, steps);
   if (sp.world > 1 && sp.rank >= 0) partition_flow_plan(fp, sp.rank, sp.world);
   return TQR_OK;
 }

@@ -66,8 +66,11 @@ struct XferPlan {
 //   Tg         the estimator's panel group-step cost in chain elements (TQR_TG, default 1.4)
 //   lazy       TQR_LAZY (default 1), la / lac: TQR_LA (default: flowplan.cpp default_la) / TQR_LAC
 //              (see build_flow_plan)
+//   depth      TQR_DEPTH: the deep-lookahead order's window in tile columns (flowplan.cpp window_order;
+//              default: flowplan.cpp default_depth); 0: the estimator's list as it is. One-rank device
+//              lists only (multi-rank plans and the host-pointer list keep theirs)
 struct FlowKnobs {
-  int seglen = 8, seglen_la = 8, la_tail = 0, tail = 0, tail_sl = 1, ualone = 0;
+  int seglen = 8, seglen_la = 8, la_tail = 0, tail = 0, tail_sl = 1, ualone = 0, depth = 0;
   double Tg = 1.4, lazy = 1.0, la = 0.0, lac = 0.0;
 };
 // The knobs of a plan of p x q tiles: the defaults of its dtype and of `world` ranks (full: each
@@ -76,7 +79,8 @@ struct FlowKnobs {
 // (TQR_SEGLEN, else by world and full); a positive value is used as it is.
 // steps > 0: a capped plan (tqr_plan_create_steps) — the defaults that count steps back from the last
 // one (tail, ualone, the multi-rank tail) count back from step steps - 1.
-FlowKnobs flow_knobs(int p, int q, int dtype, int world, bool full, int seglen, int steps = 0);
+// b: the tile size (the deep-lookahead default holds for the shape its costs were measured on; 0: off)
+FlowKnobs flow_knobs(int p, int q, int dtype, int world, bool full, int seglen, int steps = 0, int b = 0);
 // Steps of a plan of p x q tiles: min(p, q), or the cap of a capped plan (1 <= steps <= min(p, q):
 // only the leading `steps` tile columns get panels, every other column only their chains).
 inline int flow_kmax(int p, int q, int steps) { return steps > 0 ? std::min(steps, std::min(p, q)) : std::min(p, q); }
@@ -85,6 +89,10 @@ inline int flow_kmax(int p, int q, int steps) { return steps > 0 ? std::min(step
 // b / shape_ib); steps: the cap (0: none), which must be the one the knobs were made for
 void build_flow_plan(int p, int q, int ns, int ng, const FlowKnobs& kn, FlowPlan& fp, const XferPlan* xp = nullptr,
                      int steps = 0);
+// Reorder a list of panel and chain tasks (no transfers) by list scheduling with a lookahead window
+// of `depth` tile columns (flowplan.cpp). The list is replaced only by a topological permutation of
+// itself; otherwise it stays as it is.
+void window_order(std::vector<Item>& L, int p, int q, int ns, int ng, int depth);
 // TQR_DIST_PART=cyclic: the round-2 partition j % world (A/B diagnostics; default snake)
 int dist_cyclic();
 void partition_flow_plan(FlowPlan& fp, int rank, int world);

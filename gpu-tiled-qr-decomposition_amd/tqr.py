@@ -75,6 +75,9 @@ def lib():
     L.tqr_plan_info.restype = _I
     L.tqr_plan_set_tasks.argtypes = [_P, _P, _I]
     L.tqr_plan_set_tasks.restype = _I
+    if hasattr(L, "tqr_plan_get_tasks"):  # (TQR_LIB may name a build from before the call existed)
+        L.tqr_plan_get_tasks.argtypes = [_P, _P, _I]
+        L.tqr_plan_get_tasks.restype = _I
     L.tqr_plan_debug_workspace.argtypes = [_P, _I, _P, ctypes.c_size_t]
     L.tqr_plan_debug_workspace.restype = _I
     L.cudaQRFull.argtypes = [_P, _I, _I]
@@ -473,6 +476,17 @@ def plan_info(plan):
     v = [_I() for _ in range(4)]
     check(lib().tqr_plan_info(plan.h, *[ctypes.byref(x) for x in v]), "tqr_plan_info")
     return dict(zip(("engine", "ntasks", "est_order", "grid"), (x.value for x in v)))
+
+
+def plan_tasks(plan):
+    """The task list on the device of a TiledQR's flow plan (tqr_plan_get_tasks), (n, 4) int32."""
+    n = lib().tqr_plan_get_tasks(plan.h, None, 0)
+    if n < 0:
+        check(n, "tqr_plan_get_tasks")
+    items = np.zeros((n, 4), dtype=np.int32)
+    if lib().tqr_plan_get_tasks(plan.h, _ptr(items), n) != n:
+        raise TQRError("tqr_plan_get_tasks: the list changed between two calls")
+    return items
 
 
 def fill_randzo(A, m, n, seed, ldda=None, stream=None, col0=0):

@@ -139,6 +139,10 @@ int tqr_flow_list_export_steps(const tqr_flow_list_spec* spec, int steps, int* i
  * TQR_EINVAL unless it is a permutation of the plan's tasks that is topological for every
  * in-task wait (the engine's deadlock-freedom condition). Single-GPU flow plans only. */
 int tqr_plan_set_tasks(tqr_plan* plan, const int* items, int n);
+/* Diagnostics: the task list the persistent engine's workgroups dequeue, read back from the device
+ * in order (4 ints per task, at most `cap` tasks written). Returns the number of tasks of the list
+ * (this rank's), or TQR_EINVAL (no flow plan). */
+int tqr_plan_get_tasks(tqr_plan* plan, int* items, int cap);
 /* Host-only: 1 if `items` is topological for the engine's waits on an M x N tile grid, else 0. */
 int tqr_flow_order_check(int M, int N, int b, const int* items, int n);
 /* Diagnostics: copy the persistent engine's panel workspace of step k (the reflector groups'

@@ -127,16 +127,39 @@ def to_items(order):
     return np.array(out, dtype=np.int64)
 
 
-def greedy_order(M, N, ns=2, seglen=8, seglen_la=None, prm=P, prio="panel"):
+def tasks_of_items(items):
+    """The tasks of an exported list, as tasks_of names them, and its row -> segment map
+    {(k, j, i): e} (the list's own segments: tail, lone-UNMQR and lookahead segments included)."""
+    T, seg = [], {}
+    for ts, l, m, kk in items:
+        if ts & 0xff != 4:
+            T.append(("P", int(l), int(kk)))
+        else:
+            k, e, i0, i1 = int(kk) & 0xffff, int(kk) >> 16, int(l) & 0xffff, int(l) >> 16
+            T.append(("C", k, int(m), (int(ts) >> 8) & 0xff, e, i0, i1))
+            for i in range(i0, i1):
+                seg[(k, int(m), i)] = e
+    return T, seg
+
+
+def greedy_order(M, N, ns=2, seglen=8, seglen_la=None, prm=P, prio="panel", depth=0, items=None):
     """List scheduling against the model: each next list slot goes to the earliest-free
     workgroup; among tasks whose wait targets are all earlier in the list, a task whose first
     useful work could start by then is preferred by (class, step, column) — panels, then the
-    lookahead column's chains, then other chains — else the one that can start soonest."""
+    lookahead column's chains, then other chains — else the one that can start soonest.
+    prio "window" (depth D): panels (0, k, i), then the chains of the tile columns j <= k + D by
+    (1, j, k, e, s) — the columns left of the window first, so the panel front runs up to D steps
+    ahead of the bulk — then every other chain by (2, k, j, e, s). items: reorder the tasks of this
+    exported list, with its segments as they are (else the uniform segments of tasks_of)."""
     seglen_la = seglen_la or seglen
     NG, W = prm["NG"], prm["W"]
-    T = tasks_of(M, N, ns, seglen, seglen_la)
-    segl = lambda k, j: seglen_la if j == k + 1 else seglen
-    segof = lambda k, j, i: (i - k - 1) // segl(k, j)
+    if items is not None:
+        T, segmap = tasks_of_items(items)
+        segof = lambda k, j, i: segmap[(k, j, i)]
+    else:
+        T = tasks_of(M, N, ns, seglen, seglen_la)
+        segl = lambda k, j: seglen_la if j == k + 1 else seglen
+        segof = lambda k, j, i: (i - k - 1) // segl(k, j)
     # dependency (wait-target) lists
     deps = {}
     for t in T:
@@ -194,6 +217,8 @@ def greedy_order(M, N, ns=2, seglen=8, seglen_la=None, prm=P, prio="panel"):
         if t[0] == "P":
             return (0, t[2], t[1])
         _, k, j, s, e, i0, i1 = t
+        if prio == "window":
+            return (1, j, k, e, s) if j <= k + depth else (2, k, j, e, s)
         return (1 if j == k + 1 else 2, k, j, e, s)
 
     def push(t):
@@ -756,6 +781,36 @@ def main_one(argv):
 P5 = dict(P, c=16.3, e_ld=5.0, e_st=6.0, uskip=1, c0=1.5)
 
 
+# round-6 costs (profiles/r06/stamps/flowstamps_f64.txt, timeline_f64.txt): the panel group's
+# factorisation, T and trailing update, its 12 us of I/O in three parts; chain costs as P5. simulate()
+# and greedy_order() read f, bt, t, io_*, c, e_ld, e_st, disp, W, NG only. csrc/flowplan.cpp
+# window_order holds the same numbers as constants.
+P6 = dict(P, f=28.5, bt=10.3, t=15.9, io_in=4.0, io_wb=4.0, io_img=4.0, c=16.3, e_ld=5.0, e_st=6.0)
+
+
+def main_window(argv):
+    """The deep-lookahead order (flowplan.cpp window_order, TQR_DEPTH) in the one-GPU model with round-6
+    costs: the estimator's list (depth 0), the planner's list per depth (through the export) and the
+    Python greedy_order(prio="window") on the same tasks. Args: [M] [N] [depth ...] (none: the default)"""
+    M, N = _mn(argv, 64, 64)
+    depths = [int(x) for x in argv[2:]]
+    base = _list_env({"TQR_DEPTH": "0"}, M, N)
+    t0 = simulate(base, M, N, prm=P6)[0]
+    print(f"{M}x{N} tiles, round-6 costs: {len(base)} tasks; estimator's list (depth 0) {t0 / 1e3:.2f} ms", flush=True)
+    dflt = export_list(M, N)
+    same = len(dflt) == len(base) and bool((dflt == base).all())
+    print(f"  planner's default list: {'the same list' if same else f'{simulate(dflt, M, N, prm=P6)[0] / 1e3:.2f} ms'}", flush=True)
+    for D in depths:
+        cpp = _list_env({"TQR_DEPTH": str(D)}, M, N)
+        tc = simulate(cpp, M, N, prm=P6)[0]
+        line = f"  depth {D:3d}: planner {tc / 1e3:7.2f} ms ({(tc - t0) / 1e3:+.2f})"
+        if os.environ.get("TQR_SIM_PY", "1") == "1":
+            py = to_items(greedy_order(M, N, prm=P6, prio="window", depth=D, items=base))
+            tp = simulate(py, M, N, prm=P6)[0]
+            line += f", Python greedy {tp / 1e3:7.2f} ms, lists {'equal' if (py == cpp).all() else 'differ'}"
+        print(line, flush=True)
+
+
 def main_dist5(argv):
     """The 8-GPU model with round-5 chain costs (P5): one GPU at the engine's segment length 8, N
     ranks at its multi-rank default 2, and list / segment variants (environment knobs of the task
@@ -867,7 +922,7 @@ def main_calib(argv):
               f"{t8 * lo:6.1f} .. {t8 * hi:6.1f} ms, S(8) {t1 / (t8 * hi):4.2f} .. {t1 / (t8 * lo):4.2f}", flush=True)
 
 
-COMMANDS = {"calib": main_calib, "split": main_split, "dist5": main_dist5, "one": main_one, "dist": main_dist, "seglen": main_seglen, "2d": main_2d, "cp": main_cp,
+COMMANDS = {"window": main_window, "calib": main_calib, "split": main_split, "dist5": main_dist5, "one": main_one, "dist": main_dist, "seglen": main_seglen, "2d": main_2d, "cp": main_cp,
             "fastpanel": main_fastpanel, "waits": main_waits, "xcd": main_xcd}
 
 if __name__ == "__main__":
