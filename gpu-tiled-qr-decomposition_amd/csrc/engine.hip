@@ -8,7 +8,8 @@
 // into BFS waves, two launches per wave on two HIP streams joined by events.
 // This file holds:
 //   * the wave engine's kernels (k_panel: one 256-thread workgroup per GEQRT / TSQRT task; k_update:
-//     one per 64-column strip of every UNMQR / TSMQR task of the wave), k_build_t, k_randzo;
+//     one per 64-column strip of every UNMQR / TSMQR task of the wave; their bodies are wave_dev.hpp's,
+//     shared with the batched factorisation of batch.hip), k_build_t, k_randzo;
 //   * every k_flow instantiation, its LDS size and launch;
 //   * plans: creation (both engines' lists, counters, workspaces), execute, status, statistics;
 //   * multi-GPU setup (IPC export / import of the peers' workspaces and flags, the probe);
@@ -76,6 +77,7 @@ __device__ unsigned long long g_xtr[4096 * 8 * 8];  // its hand-over phase-2 mar
 #endif
 }  // namespace tqr
 #include "flow.hpp"
+#include "wave_dev.hpp"  // (after STAMP / STAMP_INIT above: the stamps build times the panel body)
 namespace tqr {
 static_assert(FST_N <= 24, "g_fst holds 24 categories per workgroup");
 static_assert(Geo<256>::TPIMG == 1024 && Geo<16>::TPIMG == 256 && Geo<256, 16>::TPIMG == 256 &&
@@ -88,174 +90,24 @@ static_assert(Geo<256>::TPK <= Geo<256>::TSZ && Geo<16>::TPK <= Geo<16>::TSZ, "p
 
 template <int B>
 __device__ __forceinline__ double* tw_ptr(const Args& a, int i, int k, int g) {
-  using G = Geo<B>;
-  return a.Tw + (((size_t)k * a.p + i) * G::NG + g) * G::TIMG;
+  return wave_tw<B>(a.Tw, a.p, i, k, g);
 }
 
 // ---------------------------------------------------------------------------------------
-// Panel kernel: GEQRT (QRS) and TSQRT (QRD) tasks, one workgroup each.
+// The wave engine's kernels: thin wrappers around the bodies of wave_dev.hpp (which the batched
+// factorisation, batch.hip, launches over many matrices). Panel kernel: GEQRT (QRS) and TSQRT (QRD)
+// tasks, one workgroup each. Update kernel: UNMQR (SAPP) and TSMQR (DAPP) on one 64-column strip.
 // ---------------------------------------------------------------------------------------
 template <int B, typename S>
 __global__ __launch_bounds__(NT, 1) void k_panel(Args a) {
-  using G = Geo<B>;
-  constexpr int IB = G::IB, VP = G::VP, TP = G::TP, NG = G::NG;
   extern __shared__ __align__(16) double lds[];
-  double* Vs = lds;
-  double* Hs = Vs + G::VSZ;
-  double* Ts = Hs + G::TSZ;
-  double* Gs = Ts + G::TSZ;
-  double* tauv = Gs + G::TSZ;
-  double* scratch = tauv + IB + 2;
-  double* Gp = scratch + 2 * 4 * 32 + 4 * 32 + 2 * 32 + G::TSZ;  // 4 partial Grams
-
-  const Item it = a.items[blockIdx.x];
-  const int type = it.ts & 0xff, l = it.l, k = it.k;
-  S* A = (S*)a.A;
-  S* tau = (S*)a.tau;
-  const size_t ldm = a.ldm;
-  const int t = threadIdx.x, w = t >> 6;
-  S* Rt = A + (size_t)k * B * ldm + (size_t)k * B;  // tile (k,k)
-  double X[G::NKS];
-  double H[G::NRI];
-
-  if (type == QRS) {
-    for (int g = 0; g < NG; ++g) {
-      const int c0 = g * IB, ks0 = c0 / 4;
-#pragma unroll 8
-      for (int idx = t; idx < B * IB; idx += NT) {
-        int r = idx % B, c = idx / B;
-        Vs[r * VP + G::pc(c)] = r >= c0 ? ld(Rt + (size_t)(c0 + c) * ldm + r) : 0.0;
-      }
-      __syncthreads();
-      panel_factor<B, false>(Vs, Hs, tauv, scratch, c0);
-      // write back R / V of the panel, taus; then make V explicit (0 above, 1 on the diagonal)
-      for (int idx = t; idx < B * IB; idx += NT) {
-        int r = idx % B, c = idx / B, d = c0 + c;
-        double v = Vs[r * VP + G::pc(c)];
-        if (r >= c0) st(Rt + (size_t)d * ldm + r, v);
-      }
-      if (t < IB) st(tau + (size_t)k * a.m + (size_t)k * B + c0 + t, tauv[t]);
-      __syncthreads();
-      for (int idx = t; idx < B * IB; idx += NT) {
-        int r = idx % B, c = idx / B, d = c0 + c;
-        if (r <= d) Vs[r * VP + G::pc(c)] = r == d ? 1.0 : 0.0;
-      }
-      __syncthreads();
-      build_t<B>(Vs, tauv, Gs, Ts, Gp, ks0);
-      double* tg = tw_ptr<B>(a, k, k, g);
-      for (int idx = t; idx < G::TSZ; idx += NT) tg[idx] = Ts[idx];
-      // trailing columns of the tile
-      const int nstr = (B - c0 - IB) / 16;
-      for (int s = w; s < nstr; s += NT / 64) {
-        asm volatile("" ::: "memory");  // keep the V-image reads inside the loop (no LICM of ~1k LDS loads)
-        const int col = c0 + IB + 16 * s;
-        load_strip<B>(X, Rt, ldm, col, ks0);
-        apply_group<B, false>(Vs, Ts, X, H, ks0);
-        store_strip<B>(X, Rt, ldm, col, ks0);
-      }
-      __syncthreads();
-    }
-  } else {  // QRD: TSQRT of [R_kk ; tile (l,k)]
-    S* Bt = A + (size_t)k * B * ldm + (size_t)l * B;
-    STAMP_INIT
-    for (int g = 0; g < NG; ++g) {
-      const int c0 = g * IB;
-#pragma unroll 8
-      for (int idx = t; idx < B * IB; idx += NT) {
-        int r = idx % B, c = idx / B;
-        Vs[r * VP + G::pc(c)] = ld(Bt + (size_t)(c0 + c) * ldm + r);
-      }
-      for (int idx = t; idx < IB * IB; idx += NT) {
-        int r = idx % IB, c = idx / IB;
-        if (r <= c) Hs[r * TP + c] = ld(Rt + (size_t)(c0 + c) * ldm + c0 + r);
-      }
-      __syncthreads();
-      STAMP(0);
-      panel_factor<B, true>(Vs, Hs, tauv, scratch, c0);
-      STAMP(1);
-      for (int idx = t; idx < B * IB; idx += NT) {
-        int r = idx % B, c = idx / B;
-        st(Bt + (size_t)(c0 + c) * ldm + r, Vs[r * VP + G::pc(c)]);
-      }
-      for (int idx = t; idx < IB * IB; idx += NT) {
-        int r = idx % IB, c = idx / IB;
-        if (r <= c) st(Rt + (size_t)(c0 + c) * ldm + c0 + r, Hs[r * TP + c]);
-      }
-      if (t < IB) st(tau + (size_t)k * a.m + (size_t)l * B + c0 + t, tauv[t]);
-      __syncthreads();
-      STAMP(2);
-      build_t<B>(Vs, tauv, Gs, Ts, Gp, 0);
-      STAMP(3);
-      double* tg = tw_ptr<B>(a, l, k, g);
-      for (int idx = t; idx < G::TSZ; idx += NT) tg[idx] = Ts[idx];
-      const int nstr = (B - c0 - IB) / 16;
-      for (int s = w; s < nstr; s += NT / 64) {
-        asm volatile("" ::: "memory");  // keep the V-image reads inside the loop (no LICM of ~1k LDS loads)
-        const int col = c0 + IB + 16 * s;
-        load_strip<B>(X, Bt, ldm, col, 0);
-        load_head<B>(H, Rt, ldm, c0, col);
-        apply_group<B, true>(Vs, Ts, X, H, 0);
-        store_strip<B>(X, Bt, ldm, col, 0);
-        store_head<B>(H, Rt, ldm, c0, col);
-      }
-      __syncthreads();
-      STAMP(4);
-    }
-  }
+  wave_panel<B, S>((S*)a.A, (S*)a.tau, a.Tw, a.items[blockIdx.x], (size_t)a.ldm, a.m, a.p, lds);
 }
 
-// ---------------------------------------------------------------------------------------
-// Update kernel: UNMQR (SAPP) and TSMQR (DAPP) on one 64-column strip, one workgroup each;
-// wave w owns columns strip*64 + 16w .. +15 of the target tile(s).
-// ---------------------------------------------------------------------------------------
 template <int B, typename S>
 __global__ __launch_bounds__(NT, 2) void k_update(Args a) {
-  using G = Geo<B>;
-  constexpr int IB = G::IB, NG = G::NG;
   extern __shared__ __align__(16) double lds[];
-  double* Vs = lds;
-  double* Ts = Vs + G::VSZ;
-
-  const Item it = a.items[blockIdx.x];
-  const int type = it.ts & 0xff, strip = it.ts >> 8, l = it.l, j = it.m, k = it.k;
-  S* A = (S*)a.A;
-  const size_t ldm = a.ldm;
-  const int w = threadIdx.x >> 6;
-  const int col = strip * 64 + 16 * w;  // strip column inside the tile
-  const bool active = col < B;
-  double X[G::NKS];
-  double H[G::NRI];
-
-  if (type == DAPP) {
-    const S* Vt = A + (size_t)k * B * ldm + (size_t)l * B;  // tile (l,k): V_B
-    S* At = A + (size_t)j * B * ldm + (size_t)k * B;        // tile (k,j): head rows
-    S* Bt = A + (size_t)j * B * ldm + (size_t)l * B;        // tile (l,j)
-    if (active) load_strip<B>(X, Bt, ldm, col, 0);
-    for (int g = 0; g < NG; ++g) {
-      __syncthreads();
-      stage_v_ts<B>(Vs, Vt, ldm, g * IB);
-      stage_t<B>(Ts, tw_ptr<B>(a, l, k, g));
-      __syncthreads();
-      if (active) {
-        load_head<B>(H, At, ldm, g * IB, col);
-        apply_group<B, true>(Vs, Ts, X, H, 0);
-        store_head<B>(H, At, ldm, g * IB, col);
-      }
-    }
-    if (active) store_strip<B>(X, Bt, ldm, col, 0);
-  } else {  // SAPP
-    const S* Vt = A + (size_t)k * B * ldm + (size_t)k * B;  // tile (k,k)
-    S* Ct = A + (size_t)j * B * ldm + (size_t)k * B;        // tile (k,j)
-    if (active) load_strip<B>(X, Ct, ldm, col, 0);
-    for (int g = 0; g < NG; ++g) {
-      __syncthreads();
-      stage_v_ge<B>(Vs, Vt, ldm, g * IB);
-      stage_t<B>(Ts, tw_ptr<B>(a, k, k, g));
-      __syncthreads();
-      if (active) apply_group<B, false>(Vs, Ts, X, H, g * IB / 4);
-    }
-    if (active) store_strip<B>(X, Ct, ldm, col, 0);
-  }
+  wave_update<B, S>((S*)a.A, a.Tw, a.items[blockIdx.x], (size_t)a.ldm, a.p, lds);
 }
 
 // T factors from a stored V and tau (for the single-tile API, where the caller hands over V
@@ -305,15 +157,7 @@ __global__ void k_randzo(S* A, int m, int n, long ldm, unsigned long long seed, 
 // ---------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------
-static size_t lds_panel(int b) {
-  int ib = b < 32 ? b : 32;
-  size_t d = (size_t)b * (ib + 2) + 8 * (size_t)ib * (ib + 1) + (ib + 2) + 2 * 4 * 32 + 4 * 32 + 2 * 32;
-  return d * sizeof(double);
-}
-static size_t lds_update(int b) {
-  int ib = b < 32 ? b : 32;
-  return ((size_t)b * (ib + 2) + (size_t)ib * (ib + 1)) * sizeof(double);
-}
+// (lds_panel, lds_update, wave_tw_bytes, wave_items: wave_dev.hpp)
 
 typedef void (*kfn)(Args);
 template <int B, typename S>
@@ -624,36 +468,16 @@ static int plan_create(tqr_plan** out, int m, int n, int b, int dtype, int rank,
   pl->dtype = dtype;
   pl->es = elem_size(dtype);
 
-  tqr_plan_t sp;
-  if (tqr_sched_plan(pl->p, pl->q, &sp) != 0) { delete pl; return TQR_ENOMEM; }
-  pl->nlevels = sp.nlevels;
-  const int nstrips = (b + 63) / 64;
   std::vector<Item> ip, iu;
-  ip.reserve(sp.ntasks);
-  iu.reserve(sp.ntasks * nstrips);
-  for (int L = 0; L < sp.nlevels; ++L) {
-    pl->off_p.push_back((long)ip.size());
-    pl->off_u.push_back((long)iu.size());
-    for (long x = sp.level_off[L]; x < sp.level_off[L + 1]; ++x) {
-      const int* tk = sp.tasks + 4 * x;
-      if (tk[0] == QRS || tk[0] == QRD) {
-        ip.push_back(Item{tk[0], tk[1], tk[2], tk[3]});
-      } else {
-        for (int s = 0; s < nstrips; ++s) iu.push_back(Item{tk[0] | (s << 8), tk[1], tk[2], tk[3]});
-      }
-    }
-  }
-  pl->off_p.push_back((long)ip.size());
-  pl->off_u.push_back((long)iu.size());
-  tqr_sched_plan_free(&sp);
+  if (!wave_items(pl->p, pl->q, b, ip, iu, pl->off_p, pl->off_u)) { delete pl; return TQR_ENOMEM; }
+  pl->nlevels = (int)pl->off_p.size() - 1;
 
-  int ib = b < 32 ? b : 32;
   if (engine == TQR_ENGINE_DEFAULT) {
     const char* eng = getenv("TQR_ENGINE");
     engine = (eng && strcmp(eng, "waves") == 0) ? TQR_ENGINE_WAVES : TQR_ENGINE_FLOW;
   }
   pl->engine = world > 1 ? TQR_ENGINE_FLOW : engine;  // the multi-GPU protocol lives in the flow engine
-  size_t tw = pl->engine == 0 ? (size_t)pl->p * pl->kmax * (b / ib) * timg_doubles(b) * sizeof(double) : 8;
+  size_t tw = pl->engine == 0 ? wave_tw_bytes(pl->p, pl->kmax, b) : 8;
   if (hipMalloc(&pl->d_items_p, std::max<size_t>(1, ip.size()) * sizeof(Item)) != hipSuccess ||
       hipMalloc(&pl->d_items_u, std::max<size_t>(1, iu.size()) * sizeof(Item)) != hipSuccess ||
       hipMalloc(&pl->d_T, tw) != hipSuccess) {

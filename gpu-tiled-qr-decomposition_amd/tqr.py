@@ -164,6 +164,20 @@ def lib():
     L.tqr_apply_pipe_form_q_ticket.restype = _I
     L.tqr_lstsq_pipe.argtypes = [_P, _P, _P, _I, _P, _I, _P, _I, _I, _P, _P]
     L.tqr_lstsq_pipe.restype = _I
+    _LL = ctypes.c_longlong
+    L.tqr_batch_create.argtypes = [ctypes.POINTER(_P), _I, _I, _I, _I, _I, ctypes.c_size_t]
+    L.tqr_batch_create.restype = _I
+    L.tqr_batch_workspace_bytes.argtypes = [_P]
+    L.tqr_batch_workspace_bytes.restype = ctypes.c_size_t
+    L.tqr_batch_group.argtypes = [_P]
+    L.tqr_batch_group.restype = _I
+    L.tqr_batch_execute.argtypes = [_P, _P, _I, _LL, _P, _LL, _P]
+    L.tqr_batch_execute.restype = _I
+    L.tqr_batch_destroy.argtypes = [_P]
+    L.tqr_batch_destroy.restype = None
+    L.tqr_batch_plan.argtypes = [_I, _I, _I, _I, _I, ctypes.c_size_t, ctypes.POINTER(_I), ctypes.POINTER(_I),
+                                 ctypes.POINTER(_I)]
+    L.tqr_batch_plan.restype = _I
     _lib = L
     return L
 
@@ -530,6 +544,76 @@ def geqrt_tiled(A, tau, b, m=None, ldda=None, stream=None):
         raise TQRError("geqrt_tiled: A and tau must be of one dtype")
     fn = lib().tqr_dgeqrt_tiled if _dtype_code(A.dtype) == TQR_F64 else lib().tqr_sgeqrt_tiled
     check(fn(m, n, b, _ptr(A), ldda, _ptr(tau), _stream_handle(stream)), "tqr_geqrt_tiled")
+
+
+class BatchedQR:
+    """Many same-shape factorisations in one call (tqr_batch, include/tqr.h "batched"): every matrix
+    of the batch comes out with the bytes of a TiledQR(engine="waves") executed on it alone, in the
+    launch count of one matrix. Create once per (m, n, b, dtype, batch); ws_limit bounds the T
+    workspace in bytes (0: 1 GiB) — a batch that needs more runs in groups of group() matrices."""
+
+    def __init__(self, m, n, b, dtype, batch, ws_limit=0):
+        self.m, self.n, self.b, self.batch = m, n, b, batch
+        self.dtype = dtype if isinstance(dtype, int) else _dtype_code(dtype)
+        self.kmax = min(m, n) // b if b > 0 else 0
+        self.h = None
+        h = _P()
+        check(lib().tqr_batch_create(ctypes.byref(h), m, n, b, self.dtype, batch, ws_limit), "tqr_batch_create")
+        self.h = h
+
+    def workspace_bytes(self):
+        return int(lib().tqr_batch_workspace_bytes(self.h))
+
+    def group(self):
+        """Matrices per launch group (tqr_batch_group)."""
+        return int(lib().tqr_batch_group(self.h))
+
+    def execute(self, A, tau, ldda=None, strideA=None, strideTau=None, stream=None):
+        """A: device tensor (batch, n, ldda), column-major per matrix as for TiledQR.execute; tau
+        (batch, kmax, m). ldda and the strides (in elements) default to those of contiguous tensors of
+        these shapes; any other layout of include/tqr.h — padded, row-interleaved — is given by ldda,
+        strideA, strideTau on a tensor whose first element is matrix 0's. Stream-ordered."""
+        if _dtype_code(A.dtype) != self.dtype or _dtype_code(tau.dtype) != self.dtype:
+            raise TQRError("BatchedQR.execute: A and tau must be of the handle's dtype")
+        if ldda is None:
+            if A.ndim != 3:  # (a flat buffer's length taken for ldda would pass the C validation)
+                raise TQRError("BatchedQR.execute: ldda defaults to the row length of a (batch, n, ldda) tensor only")
+            ldda = A.shape[-1]
+        strideA = self.n * ldda if strideA is None else strideA
+        strideTau = self.kmax * self.m if strideTau is None else strideTau
+        check(lib().tqr_batch_execute(self.h, _ptr(A), ldda, strideA, _ptr(tau), strideTau, _stream_handle(stream)),
+              "tqr_batch_execute")
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().tqr_batch_destroy(self.h)
+        except Exception:
+            pass
+
+
+def batch_plan(m, n, b, dtype, batch, ws_limit=0):
+    """Host-only: (group, ngroups, nlaunch) a BatchedQR of these arguments would use (tqr_batch_plan)."""
+    dtype = dtype if isinstance(dtype, int) else _dtype_code(dtype)
+    g, ng, nl = _I(), _I(), _I()
+    check(lib().tqr_batch_plan(m, n, b, dtype, batch, ws_limit, ctypes.byref(g), ctypes.byref(ng), ctypes.byref(nl)),
+          "tqr_batch_plan")
+    return g.value, ng.value, nl.value
+
+
+def geqrt_batched(A, tau, b, stream=None):
+    """One-shot batched factorisation of contiguous device tensors A (batch, n, m) and tau
+    (batch, kmax, m) in place: builds a BatchedQR, executes it and keeps nothing (the handle is
+    released once its work has finished)."""
+    if A.ndim != 3 or tau.ndim != 3 or tau.shape[0] != A.shape[0]:
+        raise TQRError("geqrt_batched: A must be (batch, n, m) and tau (batch, kmax, m)")
+    if not (A.is_contiguous() and tau.is_contiguous()):
+        raise TQRError("geqrt_batched: A and tau must be contiguous (BatchedQR.execute takes strides)")
+    batch, n, m = A.shape
+    bq = BatchedQR(m, n, b, A.dtype, batch)
+    if tuple(tau.shape[1:]) != (bq.kmax, m):
+        raise TQRError(f"geqrt_batched: tau must be (batch, {bq.kmax}, {m})")
+    bq.execute(A, tau, stream=stream)
 
 
 def cache_clear():

@@ -426,6 +426,67 @@ int tqr_apply_pipe_form_q_ticket(int kmax, int b, int ncols, int ticket, int* st
 int tqr_lstsq_pipe(tqr_apply_pipe* pp, tqr_solve* sv, tqr_apply* ap, int trans, const void* dA, int ldda, void* dB,
                    int nrhs, int lddb, void* dres, void* stream);
 
+/* ---- batched: many same-shape factorisations in one call --------------------------------------
+ * tqr_batch_execute factorises `batch` matrices of one shape (m, n, b, dtype) in place, each exactly
+ * as tqr_plan_execute leaves one: R, the GEQRT V, the TSQRT V_B and the compact tau.
+ * Layout: matrix i lives at dA + i * strideA elements, column-major with leading dimension ldda (one
+ * ldda for all); its compact tau (m x kmax) at dtau_compact + i * strideTau elements.
+ * Bit contract: matrix i has the bytes of a TQR_ENGINE_WAVES plan of (m, n, b, dtype) executed on
+ * that matrix alone. The bytes do not depend on batch, the group size (below), the strides, the base
+ * address or the stream. Bytes outside the matrices are not touched: rows >= m, the gaps between
+ * matrices, columns >= n; of a compact tau only what a plan's execute writes.
+ * Use of the other handles: because of the bit contract every handle of this library works on a
+ * batch member unchanged, through an offset base pointer — tqr_apply_* (prepare on dA + i * strideA,
+ * ldda, dtau_compact + i * strideTau), tqr_trsm_r, tqr_lstsq*, the pipelined solve and apply, and
+ * tqr_apply_pipe_form_q. There is no batched apply or solve.
+ * Method: the wave engine runs every BFS wave of the reference DAG as two launches (panel tasks,
+ * update strips; tqr_engine above) whose workgroups are independent of each other. The batched call
+ * issues the same launches with the matrix as a second grid dimension, so the launch count is that
+ * of one matrix and each launch holds batch times the workgroups. It uses two side streams joined to
+ * the caller's stream by events, as a wave plan does.
+ * Measured on an MI355X, fp64 (tools/batch_bench.py), against a loop of
+ * tqr_plan_execute on one wave plan and on one flow plan in the same run: 64 matrices of 512 x 512,
+ * b = 64: 2.42 ms against 130.9 and 68.1 ms; 1024 of them: 22.3 ms against 2061 and 1092 ms; 256
+ * matrices of 1024 x 1024, b = 128: 21.6 ms against 1187 and 533 ms; 256 of 4096 x 256, b = 128: 16.2
+ * ms against 1800 and 372 ms. For ONE matrix tqr_plan_execute on the default (flow) engine is the
+ * faster call (1.07 against 1.97 ms at 512 x 512, 1.46 against 6.71 ms at 4096 x 256); from 16
+ * matrices on the batched call was faster at every point measured. Matrices beyond 1024 x 1024 were
+ * not measured; one large enough to fill the device alone gains nothing from a batch.
+ * Workspace and groups: every matrix in flight needs the wave engine's T workspace, one 32 x 33 fp64
+ * image (b < 32: b x (b+1)) padded to whole KiB per 32-reflector group of every tile (l, k), k < kmax:
+ * (m/b) * kmax * (b / min(b, 32)) images. The batch therefore runs in groups of
+ *   group = min(batch, 65535, max(1, ws_limit / bytes per matrix))
+ * matrices, one group after another on the same streams (the last group may be smaller); ws_limit
+ * == 0 means 1 GiB. tqr_batch_workspace_bytes = group * bytes per matrix, allocated by create;
+ * execute allocates nothing. tqr_batch_group returns group (a NULL handle: TQR_EINVAL, and 0 bytes).
+ * Strides (elements): with batch == 1 strideA is ignored; else one of two forms, anything else is
+ * TQR_EINVAL:
+ *   stacked          strideA >= (n-1) * ldda + m: one matrix after the other;
+ *   row-interleaved  strideA >= m and (batch-1) * strideA + m <= ldda: the matrices are row blocks of
+ *                    one array under a common ldda — with strideA == m the row domains of one tall
+ *                    (batch * m) x n matrix.
+ * strideTau >= m * kmax always.
+ * Ordering: as a plan's executes. Concurrent host threads are mutually excluded while they enqueue,
+ * and each execute's stream first waits for the handle's previous execute, whatever its stream; two
+ * executes of one handle never overlap on the GPU. Stream-ordered: returns once all is enqueued.
+ * Errors: TQR_EINVAL before any device call for tqr_plan_create's own argument errors, batch < 1, a
+ * NULL handle or pointer, ldda < m or beyond the library's leading-dimension bound, and bad strides.
+ * A missing or non-gfx950 device is reported after that validation: tqr_batch_create then still
+ * returns a handle (without device memory; group and workspace_bytes answer), and every
+ * tqr_batch_execute on it returns TQR_ENODEV.
+ * tqr_batch_plan (host only, no GPU): the grouping and launch count create would choose — *group,
+ * *ngroups = ceil(batch / group), *nlaunch = ngroups * (the non-empty panel launches plus the
+ * non-empty update launches of one wave plan). Outputs may be NULL. Arguments out of range return
+ * TQR_EINVAL and write nothing. */
+typedef struct tqr_batch tqr_batch;
+int tqr_batch_create(tqr_batch** bt, int m, int n, int b, int dtype, int batch, size_t ws_limit);
+size_t tqr_batch_workspace_bytes(const tqr_batch* bt);
+int tqr_batch_group(const tqr_batch* bt); /* matrices per launch group */
+int tqr_batch_execute(tqr_batch* bt, void* dA, int ldda, long long strideA, void* dtau_compact, long long strideTau,
+                      void* stream);
+void tqr_batch_destroy(tqr_batch* bt);
+int tqr_batch_plan(int m, int n, int b, int dtype, int batch, size_t ws_limit, int* group, int* ngroups, int* nlaunch);
+
 /* ---- multi-GPU: tile-column partition, one process per GPU ---------------------------------
  * Rank r owns the tile columns j with tqr_dist_owner(j) == r — snake order over the ranks
  * (0..W-1, W-1..0, 0..W-1, ...: every rank's columns sum to the same index total, balancing the
