@@ -28,116 +28,19 @@
 namespace tqr {
 
 // ---------------------------------------------------------------------------------------
-// prepare: T_g of every GEQRT tile (k,k) and TSQRT tile (l,k), row-major IB x TP images
+// The kernels: the bodies of apply_dev.hpp (apply_t_body: one workgroup per (tile, reflector group);
+// apply_q_body: one per 64 columns of C) on the launch's own arguments
 // ---------------------------------------------------------------------------------------
 template <int B, typename S>
 __global__ __launch_bounds__(NT, 1) void k_apply_t(ApplyArgs a) {
-  using G = Geo<B>;
-  constexpr int IB = G::IB, NG = G::NG;
   extern __shared__ __align__(16) double lds[];
-  double* Vs = lds;
-  double* Ts = Vs + G::VSZ;
-  double* Gs = Ts + G::TSZ;
-  double* tauv = Gs + G::TSZ;
-  double* Gp = tauv + IB + 2;
-  // blockIdx.x = slot(l,k) * NG + g; (uniform) search of the panel the slot belongs to
-  int t = blockIdx.x / NG, k = 0;
-  while (t >= a.p - k) {
-    t -= a.p - k;
-    ++k;
-  }
-  const int l = k + t, g = blockIdx.x % NG, c0 = g * IB;
-  const bool ge = l == k;
-  const S* A = (const S*)a.A;
-  const S* tau = (const S*)a.tau;
-  const size_t ldm = a.lda;
-  const S* Vt = A + (size_t)k * B * ldm + (size_t)l * B;
-  if (ge) stage_v_ge<B>(Vs, Vt, ldm, c0);
-  else stage_v_ts<B>(Vs, Vt, ldm, c0);
-  if (threadIdx.x < IB) tauv[threadIdx.x] = ld(tau + (size_t)k * a.m + (size_t)l * B + c0 + threadIdx.x);
-  __syncthreads();
-  build_t<B>(Vs, tauv, Gs, Ts, Gp, ge ? c0 / 4 : 0);
-  double* tg = tg_ptr<B>(a, l, k, g);
-  for (int idx = threadIdx.x; idx < G::TSZ; idx += NT) tg[idx] = Ts[idx];
+  apply_t_body<B, S>(a, blockIdx.x, lds);
 }
 
-// ---------------------------------------------------------------------------------------
-// apply: C <- Q^T C (TRANS) or C <- Q C. Workgroup blockIdx.x owns columns 64 blockIdx.x ..
-// + 63, wave w its 16w .. 16w + 15. A wave with no column below nrhs does no MFMA work but
-// takes part in every barrier of the staging.
-// ---------------------------------------------------------------------------------------
 template <int B, typename S, bool TRANS>
 __global__ __launch_bounds__(NT, 2) void k_apply_q(ApplyArgs a) {
-  using G = Geo<B>;
-  constexpr int IB = G::IB, NG = G::NG;
   extern __shared__ __align__(16) double lds[];
-  double* Vs = lds;
-  double* Ts = Vs + G::VSZ;
-
-  const S* A = (const S*)a.A;
-  const size_t lda = a.lda, ldc = a.ldc;
-  // (readfirstlane: the wave index and what derives from it — the wave's C pointer — in SGPRs)
-  const int lane = threadIdx.x & 63, x = lane >> 4, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int col0 = blockIdx.x * 64 + 16 * w, col = col0 + (lane & 15);
-  const bool active = col0 < a.nrhs;  // wave-uniform
-  const bool on = col < a.nrhs;
-  // the wave's 16 columns of C (an idle wave's pointer is never used) and the lane's byte offset
-  // of (row x, its column) in them
-  S* Cw = (S*)a.C + (size_t)(active ? col0 : 0) * ldc;
-  const unsigned coff = head_off<B, S>(ldc, 0);
-  double X[G::NKS];
-  double H[G::NRI];
-
-  // UNMQR of tile (k,k) on C_k: groups ascending (Q^T) / descending (Q)
-  auto unmqr = [&](int k) {
-    const S* Vt = A + (size_t)k * B * lda + (size_t)k * B;
-    const __amdgpu_buffer_rsrc_t rk = uniform_rsrc(Cw + (size_t)k * B);
-    if (active) load_rows<B, S>(X, rk, coff, on);
-    for (int gi = 0; gi < NG; ++gi) {
-      const int g = TRANS ? gi : NG - 1 - gi;
-      __syncthreads();
-      stage_vq<B, S, true, !TRANS>(Vs, Vt, lda, g * IB);
-      stage_tq<B, !TRANS>(Ts, tg_ptr<B>(a, k, k, g));
-      __syncthreads();
-      if (active) apply_group<B, false>(Vs, Ts, X, H, g * IB / 4);
-    }
-    if (active) store_rows<B, S>(X, rk, coff, on);
-  };
-  // TSMQR of tile (l,k) on [C_k; C_l]: C_l's strip stays in registers over the groups, the 32
-  // head rows of C_k are loaded and stored per group
-  auto tsmqr = [&](int l, int k) {
-    const S* Vt = A + (size_t)k * B * lda + (size_t)l * B;
-    const __amdgpu_buffer_rsrc_t rk = uniform_rsrc(Cw + (size_t)k * B);
-    const __amdgpu_buffer_rsrc_t rl = uniform_rsrc(Cw + (size_t)l * B);
-    if (active) load_rows<B, S>(X, rl, coff, on);
-    for (int gi = 0; gi < NG; ++gi) {
-      const int g = TRANS ? gi : NG - 1 - gi;
-      __syncthreads();
-      stage_vq<B, S, false, !TRANS>(Vs, Vt, lda, g * IB);
-      stage_tq<B, !TRANS>(Ts, tg_ptr<B>(a, l, k, g));
-      __syncthreads();
-      if (active) {
-        // (Q: the head rows in reverse — this lane takes the rows of lane row 3 - x)
-        const unsigned hoff = coff + (unsigned)((g * IB + (TRANS ? 0 : 3 - 2 * x)) * (int)sizeof(S));
-        load_hrows<B, S, !TRANS>(H, rk, hoff, on);
-        apply_group<B, true>(Vs, Ts, X, H, 0);
-        store_hrows<B, S, !TRANS>(H, rk, hoff, on);
-      }
-    }
-    if (active) store_rows<B, S>(X, rl, coff, on);
-  };
-
-  if constexpr (TRANS) {
-    for (int k = 0; k < a.kmax; ++k) {
-      unmqr(k);
-      for (int l = k + 1; l < a.p; ++l) tsmqr(l, k);
-    }
-  } else {
-    for (int k = a.kmax - 1; k >= 0; --k) {
-      for (int l = a.p - 1; l > k; --l) tsmqr(l, k);
-      unmqr(k);
-    }
-  }
+  apply_q_body<B, S, TRANS>(a, blockIdx.x, lds);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -149,20 +52,7 @@ static void apply_kernels(afn* t, afn* qt, afn* qn) {
   *qt = k_apply_q<B, S, true>;
   *qn = k_apply_q<B, S, false>;
 }
-// dynamic LDS (bytes): k_apply_q holds a group's V image and T image (the engine's k_update),
-// k_apply_t the V image, T, Gram, taus and four partial Grams (the engine's k_build_t)
-static size_t lds_apply_q(int b) {
-  const int ib = b < 32 ? b : 32;
-  return ((size_t)b * (ib + 2) + (size_t)ib * (ib + 1)) * sizeof(double);
-}
-static size_t lds_apply_t(int b) {
-  const int ib = b < 32 ? b : 32;
-  return ((size_t)b * (ib + 2) + 6 * (size_t)ib * (ib + 1) + ib + 2) * sizeof(double);
-}
-static size_t timg_doubles(int b) {  // Geo<b>::TIMG
-  const size_t ib = b < 32 ? b : 32;
-  return (ib * (ib + 1) + 127) / 128 * 128;
-}
+// (lds_apply_q, lds_apply_t, timg_doubles, apply_ws_bytes: apply.hpp)
 static_assert(Geo<256>::TIMG == 1152 && Geo<16>::TIMG == 384, "host timg_doubles mirrors Geo::TIMG");
 
 }  // namespace tqr
@@ -193,8 +83,7 @@ int tqr_apply_create(tqr_apply** out, int m, int n, int b, int dtype) {
   ap->kmax = ap->p < ap->q ? ap->p : ap->q;
   ap->dtype = dtype;
   ap->es = elem_size(dtype);
-  const size_t ntiles = tile_slot(ap->kmax, ap->kmax, ap->p);  // tiles (l,k), l >= k, k < kmax
-  ap->ws_bytes = ntiles * (size_t)(b / (b < 32 ? b : 32)) * timg_doubles(b) * sizeof(double);
+  ap->ws_bytes = apply_ws_bytes(ap->p, ap->kmax, b);
   dispatch_b(b, [&](auto bb) {
     if (dtype == TQR_F64) apply_kernels<decltype(bb)::value, double>(&ap->kt, &ap->kqt, &ap->kqn);
     else apply_kernels<decltype(bb)::value, float>(&ap->kt, &ap->kqt, &ap->kqn);

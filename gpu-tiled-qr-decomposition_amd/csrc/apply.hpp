@@ -15,6 +15,27 @@ typedef void (*afn)(ApplyArgs);
 // its previous apply)
 constexpr int APPLY_NSLOT = 8;
 
+// dynamic LDS (bytes): k_apply_q holds a group's V image and T image (the engine's k_update),
+// k_apply_t the V image, T, Gram, taus and four partial Grams (the engine's k_build_t)
+static inline size_t lds_apply_q(int b) {
+  const int ib = b < 32 ? b : 32;
+  return ((size_t)b * (ib + 2) + (size_t)ib * (ib + 1)) * sizeof(double);
+}
+static inline size_t lds_apply_t(int b) {
+  const int ib = b < 32 ? b : 32;
+  return ((size_t)b * (ib + 2) + 6 * (size_t)ib * (ib + 1) + ib + 2) * sizeof(double);
+}
+static inline size_t timg_doubles(int b) {  // Geo<b>::TIMG
+  const size_t ib = b < 32 ? b : 32;
+  return (ib * (ib + 1) + 127) / 128 * 128;
+}
+// bytes of the T workspace of one factorisation of p x kmax tiles: a T image per reflector group of
+// every stored tile (l,k), l >= k, k < kmax (apply_dev.hpp tile_slot(kmax, kmax, p) of them)
+static inline size_t apply_ws_bytes(int p, int kmax, int b) {
+  const size_t ntiles = (size_t)((long long)kmax * p - (long long)kmax * (kmax - 1) / 2);
+  return ntiles * (size_t)(b / (b < 32 ? b : 32)) * timg_doubles(b) * sizeof(double);
+}
+
 }  // namespace tqr
 
 struct tqr_apply {

@@ -45,6 +45,11 @@ class Plan(ctypes.Structure):
                 ("tasks", ctypes.POINTER(_I)), ("level_off", ctypes.POINTER(ctypes.c_long))]
 
 
+class TsqrSpec(ctypes.Structure):
+    """tqr_tsqr_spec, include/tqr.h"""
+    _fields_ = [(f, _I) for f in ("m", "n", "b", "dtype", "m_dom", "fan", "nrhs_max")] + [("ws_limit", ctypes.c_size_t)]
+
+
 def lib():
     """Load libtqr.so (raises if it was not built: no fallback exists)."""
     global _lib
@@ -178,6 +183,27 @@ def lib():
     L.tqr_batch_plan.argtypes = [_I, _I, _I, _I, _I, ctypes.c_size_t, ctypes.POINTER(_I), ctypes.POINTER(_I),
                                  ctypes.POINTER(_I)]
     L.tqr_batch_plan.restype = _I
+    _SP = ctypes.POINTER(TsqrSpec)
+    L.tqr_tsqr_plan.argtypes = [_SP, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), _I,
+                                ctypes.POINTER(ctypes.c_size_t)]
+    L.tqr_tsqr_plan.restype = _I
+    L.tqr_tsqr_create.argtypes = [ctypes.POINTER(_P), _SP]
+    L.tqr_tsqr_create.restype = _I
+    L.tqr_tsqr_workspace_bytes.argtypes = [_P]
+    L.tqr_tsqr_workspace_bytes.restype = ctypes.c_size_t
+    L.tqr_tsqr_factor.argtypes = [_P, _P, _I, _P]
+    L.tqr_tsqr_factor.restype = _I
+    L.tqr_tsqr_apply_q.argtypes = [_P, _I, _P, _I, _P, _I, _I, _P]
+    L.tqr_tsqr_apply_q.restype = _I
+    L.tqr_tsqr_form_q.argtypes = [_P, _P, _I, _P, _I, _P]
+    L.tqr_tsqr_form_q.restype = _I
+    L.tqr_tsqr_lstsq.argtypes = [_P, _I, _P, _I, _P, _I, _I, _P, _P]
+    L.tqr_tsqr_lstsq.restype = _I
+    L.tqr_tsqr_level.argtypes = [_P, _I, ctypes.POINTER(_P), ctypes.POINTER(_I), ctypes.POINTER(_P), ctypes.POINTER(_I),
+                                 ctypes.POINTER(_I)]
+    L.tqr_tsqr_level.restype = _I
+    L.tqr_tsqr_destroy.argtypes = [_P]
+    L.tqr_tsqr_destroy.restype = None
     _lib = L
     return L
 
@@ -983,6 +1009,95 @@ def apply_q_host(F, T, C, b, trans=True):
     ap.apply(dF, dC, trans=trans, stream=cs)
     torch.cuda.synchronize()
     return dC.cpu().numpy()
+
+
+# ---- tall-skinny QR: a tree of batched factorisations ----------------------------------------
+class TSQR:
+    """QR of a tall-skinny m x n matrix as a tree of batched factorisations (tqr_tsqr, include/tqr.h
+    "tall-skinny"): the row domains of m_dom rows are factorised in the launches of one, their R factors
+    are stacked `fan` at a time and factorised again, up to one root. factor() leaves R of the whole
+    matrix in the upper triangle of A[0:n, 0:n] (trsm_r works on A unchanged); apply / form_q / lstsq
+    need nrhs_max >= their width (form_q: >= n). m_dom = 0 and fan = 0 take the library's defaults.
+    Calls on one handle are serialised on the GPU and need no host synchronisation in between."""
+
+    def __init__(self, m, n, b, dtype, m_dom=0, fan=0, nrhs_max=0, ws_limit=0):
+        self.m, self.n, self.b, self.nrhs_max = m, n, b, nrhs_max
+        self.dtype = dtype if isinstance(dtype, int) else _dtype_code(dtype)
+        self.h = None
+        spec = TsqrSpec(m, n, b, self.dtype, m_dom, fan, nrhs_max, ws_limit)
+        h = _P()
+        check(lib().tqr_tsqr_create(ctypes.byref(h), ctypes.byref(spec)), "tqr_tsqr_create")
+        self.h = h
+        self.m_dom, self.fan, self.levels, self.domains, _ = tsqr_plan(m, n, b, self.dtype, m_dom, fan, nrhs_max, ws_limit)
+
+    def workspace_bytes(self):
+        return int(lib().tqr_tsqr_workspace_bytes(self.h))
+
+    def level(self, l):
+        """(dW, ldw, dtau, dom_rows, ndom) of level l (tqr_tsqr_level): device addresses as ints (dW is
+        None at level 0, where the matrix is the caller's; both are None without a device)."""
+        w, t = _P(), _P()
+        ld, rows, nd = _I(), _I(), _I()
+        check(lib().tqr_tsqr_level(self.h, l, ctypes.byref(w), ctypes.byref(ld), ctypes.byref(t), ctypes.byref(rows),
+                                   ctypes.byref(nd)), "tqr_tsqr_level")
+        return w.value, ld.value, t.value, rows.value, nd.value
+
+    def _same(self, who, *tensors):
+        for t in tensors:
+            if _dtype_code(t.dtype) != self.dtype:
+                raise TQRError(f"{who}: every tensor must be of the handle's dtype")
+
+    def factor(self, A, ldda=None, stream=None):
+        """A (n, ldda), column-major as for TiledQR.execute, in place. Stream-ordered."""
+        self._same("TSQR.factor", A)
+        ldda = ldda or A.shape[-1]
+        check(lib().tqr_tsqr_factor(self.h, _ptr(A), ldda, _stream_handle(stream)), "tqr_tsqr_factor")
+
+    def apply(self, A, C, trans=True, nrhs=None, ldda=None, lddc=None, stream=None):
+        """C (nrhs, lddc) <- Q^T C (trans) or Q C in place; A as factor() left it. Stream-ordered."""
+        self._same("TSQR.apply", A, C)
+        ldda = ldda or A.shape[-1]
+        lddc = lddc or C.shape[-1]
+        nrhs = C.shape[0] if nrhs is None else nrhs
+        check(lib().tqr_tsqr_apply_q(self.h, 1 if trans else 0, _ptr(A), ldda, _ptr(C), nrhs, lddc, _stream_handle(stream)),
+              "tqr_tsqr_apply_q")
+
+    def form_q(self, A, Q, ldda=None, lddq=None, stream=None):
+        """Q (n, lddq) <- the thin Q (row j = column j of Q); output-only. Stream-ordered."""
+        self._same("TSQR.form_q", A, Q)
+        ldda = ldda or A.shape[-1]
+        lddq = lddq or Q.shape[-1]
+        check(lib().tqr_tsqr_form_q(self.h, _ptr(A), ldda, _ptr(Q), lddq, _stream_handle(stream)), "tqr_tsqr_form_q")
+
+    def lstsq(self, A, B, trans=False, nrhs=None, ldda=None, lddb=None, res=None, stream=None):
+        """tqr_tsqr_lstsq: as ApplyQ.lstsq, on the handle's own factorisation. Stream-ordered."""
+        self._same("TSQR.lstsq", A, B)
+        ldda = ldda or A.shape[-1]
+        lddb = lddb or B.shape[-1]
+        nrhs = B.shape[0] if nrhs is None else nrhs
+        pres = None if res is None else _ptr(res)
+        check(lib().tqr_tsqr_lstsq(self.h, 1 if trans else 0, _ptr(A), ldda, _ptr(B), nrhs, lddb, pres,
+                                   _stream_handle(stream)), "tqr_tsqr_lstsq")
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().tqr_tsqr_destroy(self.h)
+        except Exception:
+            pass
+
+
+def tsqr_plan(m, n, b, dtype, m_dom=0, fan=0, nrhs_max=0, ws_limit=0):
+    """Host-only: (m_dom, fan, nlevels, [D_0 .. D_{L-1}], workspace bytes) a TSQR of these arguments
+    would use (tqr_tsqr_plan)."""
+    dtype = dtype if isinstance(dtype, int) else _dtype_code(dtype)
+    spec = TsqrSpec(m, n, b, dtype, m_dom, fan, nrhs_max, ws_limit)
+    md, f, nl = _I(), _I(), _I()
+    ws = ctypes.c_size_t()
+    dom = (_I * 32)()
+    check(lib().tqr_tsqr_plan(ctypes.byref(spec), ctypes.byref(md), ctypes.byref(f), ctypes.byref(nl), dom, 32,
+                              ctypes.byref(ws)), "tqr_tsqr_plan")
+    return md.value, f.value, nl.value, list(dom[:nl.value]), int(ws.value)
 
 
 # ---- single tile ops (host pointers; the reference's SGEQRF/SLARFT/STSQRF/SSSRFT) --------

@@ -487,6 +487,92 @@ int tqr_batch_execute(tqr_batch* bt, void* dA, int ldda, long long strideA, void
 void tqr_batch_destroy(tqr_batch* bt);
 int tqr_batch_plan(int m, int n, int b, int dtype, int batch, size_t ws_limit, int* group, int* ngroups, int* nlaunch);
 
+/* ---- tall-skinny: QR of an m x n matrix, m >> n, as a tree of batched factorisations (TSQR) -------
+ * The flat tile tree of tqr_plan_execute is one GEQRT and m/b - 1 TSQRTs in series per panel: on a
+ * tall-skinny matrix the device idles behind one CU. tqr_tsqr_factor cuts A into D_0 = m / m_dom row
+ * domains, factorises them all in the launches of one (tqr_batch_execute on the row-interleaved
+ * layout), stacks the domains' R factors `fan` at a time, factorises the stacks in the same way, and so
+ * on up to one root.
+ * Shape: m >= n; b in {16, 32, 64, 128, 256} divides m and n; m_dom is a multiple of b, >= n, and
+ * divides m; fan >= 2; nrhs_max >= 0 is the widest C / B the handle's calls take (0: no C workspaces,
+ * and every apply / form_q / lstsq returns TQR_EINVAL; form_q needs nrhs_max >= n); ws_limit goes to
+ * every level's tqr_batch_create (0 = 1 GiB). Defaults: fan == 0 means 4; m_dom == 0 means the smallest
+ * multiple of b that divides m and is >= max(4 n, 1024), or m (one domain) if there is none.
+ * Levels: level 0's domains are the row blocks of A itself. Level l >= 1 has D_l = ceil(D_{l-1} / fan)
+ * domains of fan * n rows: the row blocks of the handle's workspace W_l, a (D_l * fan * n) x n
+ * column-major matrix of the handle's dtype with leading dimension D_l * fan * n. Block j of W_l (rows
+ * j n .. j n + n - 1) is the upper triangle (i <= j) of the top n x n of domain j of level l-1 with zeros
+ * below the diagonal; blocks beyond D_{l-1} (padding) are zero. All of W_l is rewritten by every factor.
+ * The last level has one domain; D_0 == 1 gives one level and no merge. Level l's compact taus are D_l
+ * blocks of (domain rows) x (n / b) elements, domain i at element i * (domain rows) * (n / b).
+ * tqr_tsqr_level returns a level's W_l (level 0: NULL, the matrix is the caller's), its leading
+ * dimension (level 0: 0), its taus, the domain height and D_l; outputs may be NULL. So domain i of
+ * level l is the member (dW + i * dom_rows, ldw, dtau + i * dom_rows * (n / b)) of shape (dom_rows, n,
+ * b), and by the bit contract every per-member handle of this library works on it through these offset
+ * pointers.
+ * On exit of tqr_tsqr_factor the upper triangle of dA[0:n, 0:n] is R of the whole matrix (only elements
+ * i <= j are written there; the V below the diagonal stays), so tqr_trsm_r works on dA unchanged. The
+ * rest of dA holds level 0's V and, in the other domains' top triangles, their R_i, which nothing reads.
+ * The Q this defines: a domain's top n rows travel up and a stack's leader is its first block, so the
+ * root's top rows trace back to rows 0 .. n-1 of A — a genuine m x m orthogonal Q with Q^T A = [R; 0]
+ * in natural row order. tqr_tsqr_apply_q: dC (m x nrhs, lddc >= m) <- Q^T dC (TQR_TRANS) or Q dC
+ * (TQR_NOTRANS) in place, with tqr_apply_q's semantics: rows >= m and columns >= nrhs are not touched;
+ * after Q^T rows 0 .. n-1 hold the "R part". Q^T applies level 0 on C's domains, gathers their top n rows
+ * into the handle's C_1 (zero padding), applies level 1 there, and so on to the root, then scatters
+ * back down; Q is the exact reverse. tqr_tsqr_form_q: the thin Q (m x n) into dQ, output-only: [I_n; 0]
+ * is filled, then Q applied (the work on its zero blocks is done). tqr_tsqr_lstsq: tqr_lstsq's semantics,
+ * dres and zeroed rows of TQR_TRANS exactly — TQR_NOTRANS: Q^T, tqr_trsm_r on rows 0 .. n-1, the residual
+ * norms of rows n .. m-1; TQR_TRANS: rows n .. zeroed, tqr_trsm_r(TQR_TRANS), Q.
+ * Bit contract: after tqr_tsqr_factor every domain of every level has the bytes of tqr_batch_execute on
+ * that layout, i.e. of a TQR_ENGINE_WAVES plan on the member alone — except the upper triangle of
+ * dA[0:n, 0:n], which holds the final R. tqr_tsqr_apply_q on a domain computes the bytes of tqr_apply_q
+ * on that member (the same kernel bodies behind a per-domain pointer offset). Nothing outside the
+ * matrices is written: rows >= m, columns >= n or nrhs, the padding of ldda / lddc.
+ * Zero padding is harmless by the tile kernels' conventions: a TSQRT on [R_kk; 0] gives V_B = 0 and
+ * tau = 2 (no scaling when |x| == 0), and zero rows of a right-hand side stay zero.
+ * Workspace: tqr_tsqr_workspace_bytes = the levels' taus, the W_l, per level and domain one tqr_apply T
+ * workspace (rebuilt by every factor, so the applies need no prepare), the C_l ((D_l * fan * n) x
+ * nrhs_max), each rounded up to 256 bytes, plus the levels' tqr_batch_workspace_bytes. create allocates
+ * it; no call allocates.
+ * Ordering: a plan's. Concurrent host threads are mutually excluded while they enqueue, and every
+ * call's stream first waits for the handle's previous call, whatever its stream (factor rewrites the T
+ * and W workspaces the applies read, the applies share the C_l). Calls return once all is enqueued.
+ * Every kernel of these calls is ordered by its launch alone — no flags, counters or waits between
+ * workgroups. More domains than a grid's y dimension (65535) run as consecutive launches.
+ * Errors: TQR_EINVAL before any device call for tqr_plan_create's own argument errors, m < n, a bad
+ * m_dom or fan, nrhs_max < 0, a shape whose grids or workspace dimensions would pass 2^31 or the
+ * leading-dimension bound, NULL pointers, a bad trans, nrhs < 1 or > nrhs_max, ldda / lddc / lddq / lddb
+ * below m or beyond the leading-dimension bound. Without a gfx950, create still returns a handle with no
+ * device memory; workspace_bytes and level's integer outputs answer (its pointers are NULL), and every
+ * enqueueing call returns TQR_ENODEV after that validation. With a device, any call other than factor
+ * before the first successful factor returns TQR_EINVAL, before any device call.
+ * Measured on an MI355X (tools/tsqr_bench.py), fp64, defaults, against tqr_plan_execute on
+ * a flow plan of the same matrix at its fastest b, and torch.geqrf, in the same run: 65536 x 256: 8.98 ms
+ * against 13.51 and 75.4 ms; 262144 x 128: 6.05 against 66.1 and 61.3 ms; 1048576 x 64: 8.42 against 521.1
+ * and 140.4 ms. tqr_tsqr_apply_q(TQR_TRANS) on 64 columns: 2.43, 1.08 and 1.42 ms against tqr_apply_pipe_q's
+ * 31.4, 120.1 and 423.5 ms on the flow factorisation; tqr_tsqr_lstsq: 2.57, 1.44 and 3.08 against
+ * tqr_lstsq_pipe's 31.6, 120.4 and 425.6 ms. The defaults are the fastest point of the sweep of m_dom x fan
+ * at all three shapes. No shape was measured at which the flow plan is the faster call; shorter matrices
+ * (below 65536 rows) and n > 256 were not measured.
+ * tqr_tsqr_plan (host only, no GPU): the resolved m_dom and fan, the level count, domains[l] = D_l (at
+ * most `cap` written) and tqr_tsqr_workspace_bytes of such a handle. Outputs may be NULL; arguments out
+ * of range return TQR_EINVAL and write nothing. */
+typedef struct tqr_tsqr tqr_tsqr;
+typedef struct tqr_tsqr_spec {
+    int m, n, b, dtype, m_dom, fan, nrhs_max;
+    size_t ws_limit;
+} tqr_tsqr_spec;
+int tqr_tsqr_plan(const tqr_tsqr_spec* spec, int* m_dom, int* fan, int* nlevels, int* domains, int cap, size_t* ws_bytes);
+int tqr_tsqr_create(tqr_tsqr** ts, const tqr_tsqr_spec* spec);
+size_t tqr_tsqr_workspace_bytes(const tqr_tsqr* ts);
+int tqr_tsqr_factor(tqr_tsqr* ts, void* dA, int ldda, void* stream);
+int tqr_tsqr_apply_q(tqr_tsqr* ts, int trans, const void* dA, int ldda, void* dC, int nrhs, int lddc, void* stream);
+int tqr_tsqr_form_q(tqr_tsqr* ts, const void* dA, int ldda, void* dQ, int lddq, void* stream); /* thin Q, m x n */
+int tqr_tsqr_lstsq(tqr_tsqr* ts, int trans, const void* dA, int ldda, void* dB, int nrhs, int lddb, void* dres,
+                   void* stream);
+int tqr_tsqr_level(const tqr_tsqr* ts, int level, void** dW, int* ldw, void** dtau, int* dom_rows, int* ndom);
+void tqr_tsqr_destroy(tqr_tsqr* ts);
+
 /* ---- multi-GPU: tile-column partition, one process per GPU ---------------------------------
  * Rank r owns the tile columns j with tqr_dist_owner(j) == r — snake order over the ranks
  * (0..W-1, W-1..0, 0..W-1, ...: every rank's columns sum to the same index total, balancing the
