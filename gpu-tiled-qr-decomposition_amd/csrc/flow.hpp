@@ -180,12 +180,7 @@ __device__ __forceinline__ bool timed_out(unsigned long long& t0, int& last, int
   return true;
 }
 
-// Multi-GPU (tile-column cyclic partition, one process per GPU): peer buffers opened by IPC.
-struct PeerBufs {
-  double* const* Wk;  // the peer's panel workspaces (IPC-opened into this process), one per k
-  int* Rf;            // the peer's member flags
-};
-
+// (PeerBufs, the multi-GPU peers' buffers: flow_list.hpp)
 struct FlowArgs {
   void* A;
   void* tau;

@@ -39,6 +39,12 @@ using ShapeW8 = FlowShape<8, 32, 1>;
 using ShapeW4 = FlowShape<4, 16, 2>;
 using ShapeR = FlowShape<4, 32, 1>;  // one 4-wave workgroup per CU, 64-column strips, 32-reflector groups (chain_res.hpp)
 
+// Multi-GPU (tile-column cyclic partition, one process per GPU): peer buffers opened by IPC.
+struct PeerBufs {
+  double* const* Wk;  // the peer's panel workspaces (IPC-opened into this process), one per k
+  int* Rf;            // the peer's member flags
+};
+
 // Multi-GPU owner of tile column j (its panel and all its updates): "snake" order over the ranks
 // (0..W-1, W-1..0, 0..W-1, ...), so that every rank's columns sum to the same index total — the
 // chain work of a column grows with its index, and the plain cyclic j % W left the last rank 11 %

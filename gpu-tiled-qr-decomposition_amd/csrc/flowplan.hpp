@@ -50,7 +50,7 @@ struct XferPlan {
 };
 
 // Order knobs of the flow task list, read from the environment ONCE per plan (flow_knobs) and
-// kept with it: the host-API task list (engine.hip plan_xfer_list, built at the first host call) and
+// kept with it: the host-API task list (hostpath.hip plan_xfer_list, built at the first host call) and
 // the device's column-final counts (xfer.hpp, from FlowArgs) must see the same segment lengths as the
 // plan's own list, whatever the environment says later.
 //   seglen     chain segment length (TQR_SEGLEN, default 8; 2 on 4+ whole-device ranks)

@@ -1,5 +1,5 @@
 // What apply.hip's tqr_lstsq and solve.hip's tqr_lstsq_fused share besides the public calls of
-// include/tqr.h: the residual-norm launch (solve.hip) and a plan's shape (engine.hip).
+// include/tqr.h: the residual-norm launch (solve.hip) and a plan's shape (plans.hip).
 #pragma once
 
 struct tqr_plan;

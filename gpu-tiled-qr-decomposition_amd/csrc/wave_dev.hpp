@@ -9,6 +9,8 @@
 //   lds_panel / lds_update / wave_tw_bytes: the kernels' dynamic LDS and a matrix's T workspace.
 // Both bodies take resolved base pointers — the matrix, its compact tau, its T workspace — so a caller
 // offsets them per matrix in 64 bits; inside a matrix the offsets are the engine's (tiles.hpp).
+// The host side is also what plans.hip (a plan's wave items and workspace) and tileapi.hip (the LDS
+// sizes of the kernels engine.hip's resolve hands them) include this header for.
 // STAMP / STAMP_INIT: the `stamps` diagnostic build of engine.hip defines them before it includes this
 // header; everywhere else they are empty.
 #pragma once
