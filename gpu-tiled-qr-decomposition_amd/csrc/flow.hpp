@@ -233,7 +233,8 @@ struct FlowArgs {
   // fp64 chains of 128- and 256-tiles on the hand-scheduled MFMA stream (chain_asm.hpp); 0: the
   // compiler-scheduled flow_chain (TQR_CHAIN_ASM=0, A/B runs); bits 0-1 the mode (1 whole next strip
   // loaded in the hand-over, 2 late loads), bit 2 UNMQR elements without the zero-row skip, bit 3
-  // fp32 storage on flow_chain32 (else flow_chain32_asm)
+  // fp32 storage on flow_chain32 (else flow_chain32_asm), bit 4 whole-line strips between steps (fp64
+  // tiles of 256 on mode 2 only: flow_list.hpp strip_permuted, TQR_STRIP_LINES)
   int chain_asm;
 };
 

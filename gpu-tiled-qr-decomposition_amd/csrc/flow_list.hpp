@@ -82,4 +82,25 @@ TQR_HD inline int seg_of_row(int k, int j, int i, int kmax, int sl, int ualone) 
   return (i - k - 1) / sl + (unmqr_alone(k, j, kmax, ualone) ? 1 : 0);
 }
 
+// Whole-line strips (plans with FlowArgs::chain_asm bit 4). The chain strip of tile
+// (i, j) stored at step k is in the whole-line layout (below) iff its next reader is a TSMQR strip
+// load, which reads with the map that wrote: the tile is neither step k+1's head row (i = k+1: its
+// UNMQR strip and every head-row access) nor its panel column (j = k+1), and step k+1 exists (kmax =
+// the plan's number of steps, a cap included). Everything else — UNMQR strips, head rows, the last
+// step, hence all that the panel, the transfers and the caller see — is the standard layout. So a
+// TSMQR strip load is whole-line at every step k >= 1 and standard at step 0.
+TQR_HD inline bool strip_permuted(int i, int j, int k, int kmax) { return i > k + 1 && j > k + 1 && k + 1 < kmax; }
+// The layouts of a wave's 16-column x 256-row fp64 strip block: the 16 B of lane (x, c) = (lane >> 4,
+// lane & 15) in row pair p's access (tile rows 8 p + 2 x, + 1 of column c) lie at byte
+//   strip_lane_off(layout, lane, col) + (p odd ? strip_odd_off(layout, col) : 0) + 64 p
+// of the block, col = the bytes between two columns. Standard (0): column c, byte 64 p + 16 x — 16
+// columns x 64 B per instruction, a column's four lanes 16 apart, which the CU's store path does not
+// merge. Whole lines (1): column 2 x + (c >> 3), + 8 for odd p, line p >> 1, piece c & 7 — 8 columns x
+// 128 B per instruction, each line from 8 consecutive lanes; a permutation of the block's 16-B pieces.
+TQR_HD inline unsigned strip_lane_off(int layout, int lane, size_t col) {
+  const unsigned x = (unsigned)lane >> 4, c = (unsigned)lane & 15;
+  return layout ? (unsigned)((2 * x + (c >> 3)) * col + 16 * (c & 7)) : (unsigned)(c * col + 16 * x);
+}
+TQR_HD inline unsigned strip_odd_off(int layout, size_t col) { return layout ? (unsigned)(8 * col - 64) : 0u; }
+
 }  // namespace tqr

@@ -706,6 +706,21 @@ int tqr_dist_plan_check(int M, int N, int b, int seglen, int rank, int world, in
   return TQR_OK;
 }
 
+int tqr_flow_strip_layout(int p, int q, int steps, int i, int j, int k) {
+  if (p < 1 || q < 1 || steps < 0 || steps > std::min(p, q)) return TQR_EINVAL;
+  const int kmax = flow_kmax(p, q, steps);
+  if (k < 0 || k >= kmax || i < k || i >= p || j <= k || j >= q) return TQR_EINVAL;  // (a chain strip of step k)
+  return strip_permuted(i, j, k, kmax) ? 1 : 0;
+}
+
+long tqr_flow_strip_offset(int layout, int pair, int lane, long ld) {
+  if ((layout != 0 && layout != 1) || pair < 0 || pair >= 32 || lane < 0 || lane >= 64 || ld < 256 ||
+      (size_t)ld * 8 * 16 >= ((size_t)1 << 31))
+    return TQR_EINVAL;
+  const size_t col = (size_t)ld * 8;
+  return (long)(strip_lane_off(layout, lane, col) + ((pair & 1) ? strip_odd_off(layout, col) : 0u) + 64u * (unsigned)pair);
+}
+
 int tqr_flow_strip_width(void) { return shape_info(flow_shape(TQR_F64, 256)).sw; }
 
 int tqr_flow_order_check(int M, int N, int b, const int* items, int n) {

@@ -173,6 +173,13 @@ int plan_create(tqr_plan** out, int m, int n, int b, int dtype, int rank, int wo
     if (const char* eu = getenv("TQR_UNMQR_SKIP"); eu && atoi(eu) == 0 && pl->chain_asm) pl->chain_asm |= 4;
     // (bit 3: fp32 storage on the compiler-scheduled flow_chain32; A/B only)
     if (const char* e32 = getenv("TQR_CHAIN32_ASM"); e32 && atoi(e32) == 0) pl->chain_asm |= 8;
+    // (bit 4: whole-line strips between steps, flow_list.hpp strip_permuted — only the form that knows
+    // the layout: the fp64 generated chain with late strip loads, 8-wave shape, tiles of 256, at any
+    // number of ranks; TQR_STRIP_LINES=0 keeps every strip standard, A/B runs)
+    if (dtype == TQR_F64 && b == 256 && pl->shape == 8 && (pl->chain_asm & 3) == 2) {
+      const char* el = getenv("TQR_STRIP_LINES");
+      if (!el || atoi(el) != 0) pl->chain_asm |= 16;
+    }
     build_flow_plan(pl->p, pl->q, pl->ns, pl->ng, pl->knobs, fp, nullptr, steps);
     pl->nflow_global = (int)fp.items.size();
     pl->list_hash = flow_list_hash(fp.items);  // of the global list: the ranks must agree on it (tqr_dist_import)

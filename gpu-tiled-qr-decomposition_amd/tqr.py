@@ -83,6 +83,11 @@ def lib():
     if hasattr(L, "tqr_plan_get_tasks"):  # (TQR_LIB may name a build from before the call existed)
         L.tqr_plan_get_tasks.argtypes = [_P, _P, _I]
         L.tqr_plan_get_tasks.restype = _I
+    if hasattr(L, "tqr_flow_strip_layout"):
+        L.tqr_flow_strip_layout.argtypes = [_I] * 6
+        L.tqr_flow_strip_layout.restype = _I
+        L.tqr_flow_strip_offset.argtypes = [_I, _I, _I, ctypes.c_long]
+        L.tqr_flow_strip_offset.restype = ctypes.c_long
     L.tqr_plan_debug_workspace.argtypes = [_P, _I, _P, ctypes.c_size_t]
     L.tqr_plan_debug_workspace.restype = _I
     L.cudaQRFull.argtypes = [_P, _I, _I]
@@ -509,6 +514,24 @@ def flow_list(M, N, b, dtype=TQR_F64, seglen=0, world=1, rank=-1, full=1, nxc=0,
     if export(_ptr(items), n) != n:
         raise TQRError("tqr_flow_list_export: the list changed between two calls")
     return items
+
+
+def strip_layout(p, q, steps, i, j, k):
+    """Host-only: the layout (0 standard, 1 whole lines) in which a whole-line plan of p x q tiles with
+    `steps` steps (0 = all) stores the chain strips of tile (i, j) at step k (tqr_flow_strip_layout)."""
+    r = lib().tqr_flow_strip_layout(p, q, steps, i, j, k)
+    if r < 0:
+        check(r, "tqr_flow_strip_layout")
+    return r
+
+
+def strip_offset(layout, pair, lane, ld):
+    """Host-only: byte offset of lane `lane`'s 16 bytes of row pair `pair` inside a wave's 16-column
+    strip block under `layout`, leading dimension ld elements (tqr_flow_strip_offset)."""
+    r = lib().tqr_flow_strip_offset(layout, pair, lane, ld)
+    if r < 0:
+        check(r, "tqr_flow_strip_offset")
+    return r
 
 
 def plan_info(plan):

@@ -115,6 +115,17 @@ int tqr_flow_strip_width(void);
  * {type | strip << 8, l, m, k} (chains: type 4, l = i0 | i1 << 16, k = step | segment << 16);
  * returns the number of tasks (writes at most `cap`). */
 int tqr_flow_plan_export(int M, int N, int b, int seglen, int* items, int cap);
+/* Whole-line strips of the fp64 engine (tiles of 256): the layout, 0 standard or 1 whole lines, in
+ * which the chain strips of tile (i, j) — i >= k (i = k: the UNMQR element), j > k — are stored at
+ * step k of a p x q tile plan with `steps` steps (0 = all), where the plan has them on
+ * (TQR_STRIP_LINES); the function the kernel evaluates. A tile's next reader expects what this gives
+ * for its last writer; 1 only for tiles that a TSMQR element of step k + 1 reads next, so the
+ * caller, the panel and the transfers see standard tiles only. TQR_EINVAL outside the plan.
+ * tqr_flow_strip_offset: the byte offset, inside a wave's 16-column x 256-row block of a matrix with
+ * leading dimension ld (elements), of the 16 bytes that lane `lane` of the wave moves in its access
+ * of row pair `pair` (0..31) under that layout. */
+int tqr_flow_strip_layout(int p, int q, int steps, int i, int j, int k);
+long tqr_flow_strip_offset(int layout, int pair, int lane, long ld);
 /* Host-only: the task list of any plan, in the same 4-int form — exactly the list
  * tqr_plan_create / tqr_dist_plan_create builds for the spec (nxc = 0), or the host-pointer API's
  * list with nxc upload / download tasks per tile column (nxc 1..255, one-GPU plans only).

@@ -12,7 +12,8 @@
 // the hand-overs of the CUs are spread over the group positions as in the engine, 128 = the next strip
 // loaded from a tile 33 rows of tiles away (not the row block right below the stored one), 256 = the
 // hand-over loads only the next strip's first TQR_CHAIN_ASM_XLEAD_B* row pairs, the next element's
-// first body the rest inside its phase 1 (TQR_CHAIN_ASM=2 in the engine).
+// first body the rest inside its phase 1 (TQR_CHAIN_ASM=2 in the engine), 512 = every strip stored and
+// loaded in the whole-line layout (flow_list.hpp strip_lane_off; the engine's TQR_STRIP_LINES).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../include -I../../gpu-tiled-qr-decomposition_amd/csrc chain_asm_bench.hip -o chain_asm_bench
 #include <hip/hip_runtime.h>
 
@@ -81,6 +82,7 @@ __global__ __launch_bounds__(512, 1) void k_asm(double* X0, double* H0, const do
       o.vt = vb + ot;
       o.vl16 = vl16;
       o.loff = loff;
+      o.standard_strips();
       o.bpa = coal_bpa(lane);  // (used by GEN_COALESCE bodies only)
       o.loffc = coal_off(lane, ldm);
       o.hoff = __builtin_amdgcn_readfirstlane((int)(8 * ldm * 8));
@@ -127,6 +129,11 @@ __global__ __launch_bounds__(512, 1) void k_asm(double* X0, double* H0, const do
       o.vt = vb + ot;
       o.vl16 = vl16;
       o.loff = loff;
+      o.standard_strips();
+      if (MODE & 512) {
+        o.va0 = o.va1 = strip_lane_off(1, lane, (size_t)ldm * 8);
+        o.xso = o.xs = sreg(strip_odd_off(1, (size_t)ldm * 8));
+      }
       o.bpa = coal_bpa(lane);  // (used by GEN_COALESCE bodies only)
       o.loffc = coal_off(lane, ldm);
       o.hoff = __builtin_amdgcn_readfirstlane((int)(8 * ldm * 8));
@@ -230,6 +237,11 @@ __global__ __launch_bounds__(256, 1) void k_asm4(double* X0, double* H0, const d
       o.vt = vb + ot;
       o.vl16 = vl16;
       o.loff = loff;
+      o.standard_strips();
+      if (MODE & 512) {
+        o.va0 = o.va1 = strip_lane_off(1, lane, (size_t)ldm * 8);
+        o.xso = o.xs = sreg(strip_odd_off(1, (size_t)ldm * 8));
+      }
       o.bpa = coal_bpa(lane);  // (used by GEN_COALESCE bodies only)
       o.loffc = coal_off(lane, ldm);
       o.hoff = __builtin_amdgcn_readfirstlane((int)(8 * ldm * 8));
@@ -426,6 +438,16 @@ int main(int argc, char** argv) {
     if (run<264 + 64 + 16>(X, H, img, ncu, nelem, clk)) return 1;
     if (run<264 + 64 + 32>(X, H, img, ncu, nelem, clk)) return 1;
     if (run<264 + 64 + 1>(X, H, img, ncu, nelem, clk)) return 1;
+  } else if (sel == 7) {  // whole-line strips against the standard layout (late-load hand-over), twice, and
+                          // the same with the stores dropped: lockstep, then desynchronised
+    for (int r = 0; r < 2; ++r) {
+      if (run<264>(X, H, img, ncu, nelem, clk)) return 1;
+      if (run<264 + 512>(X, H, img, ncu, nelem, clk)) return 1;
+    }
+    if (run<264 + 16>(X, H, img, ncu, nelem, clk)) return 1;
+    if (run<264 + 64>(X, H, img, ncu, nelem, clk)) return 1;
+    if (run<264 + 64 + 512>(X, H, img, ncu, nelem, clk)) return 1;
+    if (run<264 + 64 + 16>(X, H, img, ncu, nelem, clk)) return 1;
   } else if (sel == 2) {  // late strip loads vs the whole strip in the hand-over
     if (run<8>(X, H, img, ncu, nelem, clk)) return 1;
     if (run<264>(X, H, img, ncu, nelem, clk)) return 1;

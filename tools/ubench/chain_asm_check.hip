@@ -61,6 +61,7 @@ __global__ __launch_bounds__(512, 1) void k_group(const double* img, double* X, 
     o.vt = lds0 + (unsigned)(G::VIMG * 8 + (x * 4 + y) * NRI * 8);
     o.vl16 = 16u * lane;
     o.loff = loff;
+    o.standard_strips();
     o.svsrc = uni(img);
     o.stsrc = uni(img + G::VIMG);
     o.sdst = sreg(lds0 + BUF * 8);
@@ -136,6 +137,7 @@ __global__ __launch_bounds__(512, 1) void k_elem(const double* img, double* X, d
       o.vt = vb + (unsigned)(G::VIMG * 8 + (x * 4 + y) * NRI * 8);
       o.vl16 = vl16;
       o.loff = loff;
+      o.standard_strips();
       o.svsrc = uni(img + (size_t)gn * BUF);
       o.stsrc = uni(img + (size_t)gn * BUF + G::VIMG);
       o.sdst = sreg(lds0 + (unsigned)((buf ^ 1) * BUF * 8));

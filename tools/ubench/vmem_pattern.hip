@@ -34,6 +34,63 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p) {
 // +16: 1 column per instruction (1 KiB = 128 rows), +32: 4 columns x 256 B, +64: 8 columns x 128 B,
 // +128: the strip's own 16 columns x 64 B per instruction, but the 4 lanes of a column consecutive;
 // +256 / +512: the strip layout moved by ds_bpermute to +128's / to 8 columns x 128 B (stores only)
+// +1024 / +2048: the strip's own lanes and registers, only the addresses permuted inside the wave's
+// 16 x 256 block (strip_lines_off below) so that every instruction covers 8 whole 128-B lines:
+// +1024 swaps 64-B half lines between the partner instructions 2q / 2q + 1 (a line's 8 pieces come
+// from lanes c, c + 16, c + 32, c + 48 and c + 8, ... : not adjacent), +2048 puts the 8 lanes
+// (x, 8 hh .. 8 hh + 7) of an instruction on one line (16-B pieces permuted, lanes adjacent)
+// Byte offset of lane (x, c)'s 16-B piece of store instruction p (row pair p: rows 8 p + 2 x, + 1 of
+// column c) relative to the wave's block. The per-instruction immediate stays 64 p; the lane offset
+// depends on the parity of p only (one more VGPR operand in the chain).
+//   kind 0: standard     column c,                 byte 64 p + 16 x
+//   kind 1: half-line swap: instruction 2q takes line q of columns 0-7, 2q + 1 that of columns 8-15;
+//           lanes c >= 8 of 2q and lanes c < 8 of 2q + 1 trade places (column c -+ 8, other half)
+//   kind 2: lane-ordered: instruction 2q, lanes (x, 8 hh + i) -> column 2 x + hh (+ 8 for 2q + 1),
+//           line q, piece i
+__host__ __device__ inline unsigned strip_lines_off(int kind, int p, int x, int c, long ldm) {
+  const unsigned col = (unsigned)(ldm * 8), imm = 64u * (unsigned)p;
+  unsigned lo;
+  if (kind == 1) {
+    if (!(p & 1)) lo = c < 8 ? c * col + 16u * x : (c - 8) * col + 64u + 16u * x;
+    else lo = c >= 8 ? c * col + 16u * x : (c + 8) * col - 64u + 16u * x;
+  } else if (kind == 2) {
+    lo = (2 * x + (c >> 3) + ((p & 1) ? 8 : 0)) * col + 16u * (c & 7) - ((p & 1) ? 64u : 0u);
+  } else {
+    lo = c * col + 16u * x;
+  }
+  return lo + imm;
+}
+
+// host check of a kind: a bijection on the block's 2048 16-B pieces, every instruction's 64
+// addresses 8 aligned 128-B runs, everything inside the 16 columns x 2 KiB block
+static bool strip_lines_check(int kind, long ldm) {
+  static unsigned char seen[16][128];
+  for (auto& r : seen)
+    for (auto& v : r) v = 0;
+  for (int p = 0; p < 32; ++p) {
+    unsigned long long lines[8];
+    int nl = 0, cnt[8] = {0};
+    for (int l = 0; l < 64; ++l) {
+      const unsigned o = strip_lines_off(kind, p, l >> 4, l & 15, ldm);
+      const unsigned cc = o / (unsigned)(ldm * 8), b = o % (unsigned)(ldm * 8);
+      if (cc >= 16 || b >= 2048 || b % 16) return false;
+      if (seen[cc][b / 16]++) return false;
+      const unsigned long long ln = ((unsigned long long)cc << 32) | (b / 128);
+      int i = 0;
+      while (i < nl && lines[i] != ln) ++i;
+      if (i == nl) {
+        if (nl == 8) return kind == 0;  // (standard: 16 half lines)
+        lines[nl++] = ln;
+      }
+      ++cnt[i];
+    }
+    if (kind != 0)
+      for (int i = 0; i < 8; ++i)
+        if (cnt[i] != 8) return false;
+  }
+  return true;
+}
+
 template <int MODE, int SAUX = 16>
 __global__ __launch_bounds__(512, 1) void k_io(double* X, long ldm, int rep, unsigned long long* clk) {
   const int t = threadIdx.x, w = t >> 6, lane = t & 63, x = lane >> 4, c = lane & 15;
@@ -53,6 +110,8 @@ __global__ __launch_bounds__(512, 1) void k_io(double* X, long ldm, int rep, uns
     double* base = X + (size_t)(blockIdx.x * 128 + 16 * w) * ldm + (size_t)(e % 32) * 256;
     const __amdgpu_buffer_rsrc_t so = rsrc(base), si = rsrc(base + 256);
     auto o = [&](int p) {
+      if (MODE & 1024) return strip_lines_off(1, p, x, c, ldm);
+      if (MODE & 2048) return strip_lines_off(2, p, x, c, ldm);
       if (MODE & 128) return (unsigned)(((size_t)(lane >> 2) * ldm + 8 * p + 2 * (lane & 3)) * 8);
       if (MODE & 16) return (unsigned)((size_t)(p / 2) * ldm * 8 + (p % 2) * 1024 + lane * 16);
       if (MODE & 32) return (unsigned)(((size_t)(4 * (p % 4) + lane / 16) * ldm + 32 * (p / 4) + 2 * (lane % 16)) * 8);
@@ -119,7 +178,7 @@ static int run(double* X, long ldm, int nwg, int rep, unsigned long long* clk) {
   const double kib = ((MODE & 3) == 3 ? 2.0 : 1.0) * NP * 8;  // KiB per workgroup per element
   printf("aux %2d mode %2d (%s, %s) %3d WG: %.2f us per element per WG, %.1f GB/s per CU\n", SAUX, MODE,
          (MODE & 3) == 1 ? "stores" : (MODE & 3) == 2 ? "loads " : "both  ",
-         (MODE & 256) ? "bperm->quad" : (MODE & 512) ? "bperm->line" : (MODE & 128) ? "16x64B quad" : (MODE & 16) ? "1 col/insn" : (MODE & 32) ? "4 col/insn" : (MODE & 64) ? "8 col/insn" : (MODE & 8) ? "contiguous"
+         (MODE & 1024) ? "half-line swap" : (MODE & 2048) ? "lane-ordered" : (MODE & 256) ? "bperm->quad" : (MODE & 512) ? "bperm->line" : (MODE & 128) ? "16x64B quad" : (MODE & 16) ? "1 col/insn" : (MODE & 32) ? "4 col/insn" : (MODE & 64) ? "8 col/insn" : (MODE & 8) ? "contiguous"
          : (MODE & 4) ? "full lines" : "half lines", nwg, us, kib * 1024 / us / 1e3);
   return 0;
 }
@@ -135,6 +194,32 @@ int main(int argc, char** argv) {
   CK(hipMemset(X, 0, (size_t)ncu * 128 * ldm * 8));
   unsigned long long* clk;
   CK(hipMalloc(&clk, sizeof(unsigned long long) * 1024));
+  if (argc > 2 && atoi(argv[2]) == 3) {  // address-permuted strips (whole lines without lane moves)
+    if (ldm % 16) {
+      printf("ldm must be a multiple of 16 doubles (128-B lines)\n");
+      return 1;
+    }
+    for (int kind : {0, 1, 2}) {
+      if (!strip_lines_check(kind, ldm)) {
+        printf("layout %d: not a bijection of whole lines\n", kind);
+        return 1;
+      }
+    }
+    for (int nwg : {1, ncu}) {
+      if (run<1>(X, ldm, nwg, rep, clk)) return 1;
+      if (run<1 + 64>(X, ldm, nwg, rep, clk)) return 1;
+      if (run<1 + 1024>(X, ldm, nwg, rep, clk)) return 1;
+      if (run<1 + 2048>(X, ldm, nwg, rep, clk)) return 1;
+      if (run<2>(X, ldm, nwg, rep, clk)) return 1;
+      if (run<2 + 1024>(X, ldm, nwg, rep, clk)) return 1;
+      if (run<2 + 2048>(X, ldm, nwg, rep, clk)) return 1;
+      if (run<3>(X, ldm, nwg, rep, clk)) return 1;
+      if (run<3 + 64>(X, ldm, nwg, rep, clk)) return 1;
+      if (run<3 + 1024>(X, ldm, nwg, rep, clk)) return 1;
+      if (run<3 + 2048>(X, ldm, nwg, rep, clk)) return 1;
+    }
+    return 0;
+  }
   if (argc > 2 && atoi(argv[2]) == 2) {  // columns per instruction (round 6)
     for (int nwg : {1, ncu}) {
       if (run<1 + 128>(X, ldm, nwg, rep, clk)) return 1;
