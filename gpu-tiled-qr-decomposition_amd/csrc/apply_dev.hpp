@@ -122,8 +122,9 @@ __device__ __forceinline__ void stage_vq(double* Vs, const S* __restrict__ vt, s
 
 // ---------------------------------------------------------------------------------------
 // The bodies of the two whole-factorisation kernels, on resolved arguments: apply.hip's k_apply_t /
-// k_apply_q call them with blockIdx.x, tsqr.hip's k_apply_t_batch / k_apply_q_batch with the base
-// pointers of domain blockIdx.y — the same code on the same operands, so the same bits.
+// k_apply_q call them with blockIdx.x, apply_batch_dev.hpp's k_apply_t_batch / k_apply_q_batch (tsqr.hip,
+// batch_apply.hip) with the base pointers of member blockIdx.y — the same code on the same operands, so
+// the same bits.
 // ---------------------------------------------------------------------------------------
 // ---------------------------------------------------------------------------------------
 // prepare: T_g of every GEQRT tile (k,k) and TSQRT tile (l,k), row-major IB x TP images

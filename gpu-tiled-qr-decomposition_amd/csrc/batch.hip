@@ -16,6 +16,7 @@
 #include <new>
 #include <vector>
 
+#include "batch_layout.hpp"
 #include "host_common.hpp"
 #include "tqr.h"
 #include "wave_dev.hpp"
@@ -210,14 +211,8 @@ int tqr_batch_group(const tqr_batch* bt) { return bt ? bt->group : TQR_EINVAL; }
 int tqr_batch_execute(tqr_batch* bt, void* dA, int ldda, long long strideA, void* dtau, long long strideTau, void* stream) {
   if (!bt || !dA || !dtau || ldda < bt->m || !valid_ld(ldda, bt->es)) return TQR_EINVAL;
   if (strideTau < (long long)bt->m * bt->kmax) return TQR_EINVAL;
-  if (bt->batch == 1) {
-    strideA = 0;  // ignored
-  } else {
-    const bool stacked = strideA >= (long long)(bt->n - 1) * ldda + bt->m;
-    // (strideA <= ldda first: the product below then stays far inside 64 bits)
-    const bool interleaved = strideA >= bt->m && strideA <= ldda && (long long)(bt->batch - 1) * strideA + bt->m <= ldda;
-    if (!stacked && !interleaved) return TQR_EINVAL;
-  }
+  if (!batch_stride_ok(bt->m, bt->n, bt->batch, ldda, strideA)) return TQR_EINVAL;  // batch_layout.hpp
+  if (bt->batch == 1) strideA = 0;                                                  // ignored
   if (!bt->ready) return TQR_ENODEV;
   hipStream_t cs = (hipStream_t)stream;
   std::lock_guard<std::mutex> lk(bt->mu);

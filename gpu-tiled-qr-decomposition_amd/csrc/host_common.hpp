@@ -1,5 +1,5 @@
 // Host helpers every HIP unit of the library uses (engine.hip and the plan units through plan.hpp,
-// apply.hip, apply_pipe.hip, solve.hip, solve_pipe.hip, batch.hip, tsqr.hip): the error macro, the device check, the argument bounds of include/tqr.h and the
+// apply.hip, apply_pipe.hip, solve.hip, solve_pipe.hip, batch.hip, tsqr.hip, batch_apply.hip): the error macro, the device check, the argument bounds of include/tqr.h and the
 // dispatch on the tile size. Header-only; it includes HIP, so the planner (flowplan.cpp, built by g++)
 // never sees it — the one thing the two share, valid_b, lives in flow_list.hpp.
 #pragma once

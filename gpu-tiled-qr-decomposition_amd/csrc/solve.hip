@@ -24,108 +24,17 @@
 
 namespace tqr {
 
-struct SolveArgs {
-  const void* A;  // factorised matrix (S*): R in the upper triangle of the leading n x n block
-  void* X;        // n x nrhs (S*)
-  long lda, ldx;
-  int nt, nrhs;   // nt = n / b tile rows
-};
-
-// (the operand images stage_r, the substitution subst and the strip loads load_h / load_x, which
+// (SolveArgs and the kernel's body trsm_r_body, which batch_apply.hip's k_trsm_r_batch shares, and the
+// operand images stage_r, the substitution subst and the strip loads load_h / load_x, which
 // solve_pipe.hip's kernel shares: solve_dev.hpp)
 
 // ---------------------------------------------------------------------------------------
-// solve: X <- R^{-T} X (TRANS) or X <- R^{-1} X. Workgroup blockIdx.x owns columns 64 blockIdx.x ..
-// + 63, wave w its 16w .. 16w + 15. A wave with no column below nrhs does no arithmetic but takes
-// part in the staging and in every barrier.
+// solve: trsm_r_body on the launch's own arguments, one workgroup per 64 columns of X
 // ---------------------------------------------------------------------------------------
 template <int B, typename S, bool TRANS>
 __global__ __launch_bounds__(NT, 2) void k_trsm_r(SolveArgs a) {
-  using G = Geo<B>;
-  constexpr int IB = G::IB, NG = G::NG, NRI = G::NRI, NKS = G::NKS;
   extern __shared__ __align__(16) double lds[];
-  double* Vs = lds;
-
-  const S* A = (const S*)a.A;
-  const size_t lda = a.lda, ldx = a.ldx;
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int col0 = blockIdx.x * 64 + 16 * w, col = col0 + (lane & 15);
-  const bool active = col0 < a.nrhs;  // wave-uniform
-  const bool on = col < a.nrhs;
-  S* Xw = (S*)a.X + (size_t)(active ? col0 : 0) * ldx;
-  const unsigned coff = head_off<B, S>(ldx, 0);
-  double X[NKS];
-
-  // tile (k,k) against X_k: per group (descending for R, ascending for R^T) first the groups
-  // already solved — Z = X_g - (their columns of the group's rows of op(R)) X, the MFMA product over
-  // those k-steps only — then the group's own block by substitution
-  auto diag = [&](int k) {
-    const S* Rt = A + (size_t)k * B * lda + (size_t)k * B;
-    for (int gi = 0; gi < NG; ++gi) {
-      const int g = TRANS ? gi : NG - 1 - gi;
-      __syncthreads();
-      stage_r<B, S, !TRANS, true>(Vs, Rt, lda, g, TRANS ? 0 : g, TRANS ? g + 1 : NG);
-      __syncthreads();
-      if (active) {
-        // (the group's registers by selects on the uniform g: X stays in registers at any NG)
-        double Z[NRI];
-#pragma unroll
-        for (int r = 0; r < NRI; ++r) Z[r] = X[r];
-#pragma unroll
-        for (int gg = 1; gg < NG; ++gg)
-#pragma unroll
-          for (int r = 0; r < NRI; ++r) Z[r] = gg == g ? X[gg * NRI + r] : Z[r];
-        accum_z<B>(Vs, X, Z, TRANS ? 0 : (g + 1) * NRI, TRANS ? g * NRI : NKS);
-        subst<B, TRANS>(Vs + g * IB * G::VP, Z);
-#pragma unroll
-        for (int gg = 0; gg < NG; ++gg)
-#pragma unroll
-          for (int r = 0; r < NRI; ++r) X[gg * NRI + r] = gg == g ? Z[r] : X[gg * NRI + r];
-      }
-    }
-  };
-  // X_i -= (tile Rt of op(R)) X_k: per group the 32 target rows are loaded ahead of the staging,
-  // updated by one pass of accum_z over the whole strip and stored
-  auto update = [&](int i, const S* Rt) {
-    const __amdgpu_buffer_rsrc_t ri = uniform_rsrc(Xw + (size_t)i * B);
-    for (int g = 0; g < NG; ++g) {
-      double H[NRI];
-      const unsigned hoff = coff + (unsigned)(g * IB * (int)sizeof(S));
-      if (active) load_h<B, S>(H, ri, hoff, on);
-      __syncthreads();
-      stage_r<B, S, !TRANS, false>(Vs, Rt, lda, g, 0, NG);
-      __syncthreads();
-      if (active) {
-        accum_z<B>(Vs, X, H, 0, NKS);
-        if (on) store_head_buf<B, S, 0>(H, ri, hoff);
-      }
-    }
-  };
-  auto step = [&](int k) {
-    const __amdgpu_buffer_rsrc_t rk = uniform_rsrc(Xw + (size_t)k * B);
-    if (active) load_x<B, S>(X, rk, coff, on);
-    diag(k);
-    if (active) {
-      // fp32 storage: the updates use X_k as it is stored
-      if constexpr (sizeof(S) == 4) {
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks) X[ks] = (double)(float)X[ks];
-      }
-      if (on) store_strip_buf<B, S, 0>(X, rk, coff, 0);
-    }
-  };
-
-  if constexpr (TRANS) {
-    for (int k = 0; k < a.nt; ++k) {
-      step(k);
-      for (int i = k + 1; i < a.nt; ++i) update(i, A + (size_t)i * B * lda + (size_t)k * B);  // R_ki
-    }
-  } else {
-    for (int k = a.nt - 1; k >= 0; --k) {
-      step(k);
-      for (int i = 0; i < k; ++i) update(i, A + (size_t)k * B * lda + (size_t)i * B);  // R_ik
-    }
-  }
+  trsm_r_body<B, S, TRANS>(a, blockIdx.x, lds);
 }
 
 // ---------------------------------------------------------------------------------------

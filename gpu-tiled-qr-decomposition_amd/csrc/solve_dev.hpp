@@ -1,6 +1,7 @@
-// Device helpers of the triangular solve with R, shared by its two kernels: solve.hip's k_trsm_r (one
-// workgroup per strip) and solve_pipe.hip's k_trsm_r_pipe (one workgroup per strip and tile row).
-// Both build the same operand images and run the same substitution, so they compute the same bits.
+// Device helpers of the triangular solve with R, shared by its kernels: solve.hip's k_trsm_r (one
+// workgroup per strip), batch_apply.hip's k_trsm_r_batch (the same body, trsm_r_body below, per strip and
+// batch member) and solve_pipe.hip's k_trsm_r_pipe (one workgroup per strip and tile row).
+// All build the same operand images and run the same substitution, so they compute the same bits.
 #pragma once
 #include "tiles.hpp"
 
@@ -142,6 +143,109 @@ __device__ __forceinline__ void load_x(double (&X)[Geo<B>::NKS], __amdgpu_buffer
   } else {
 #pragma unroll
     for (int ks = 0; ks < Geo<B>::NKS; ++ks) X[ks] = 0.0;
+  }
+}
+
+struct SolveArgs {
+  const void* A;  // factorised matrix (S*): R in the upper triangle of the leading n x n block
+  void* X;        // n x nrhs (S*)
+  long lda, ldx;
+  int nt, nrhs;   // nt = n / b tile rows
+};
+
+// ---------------------------------------------------------------------------------------
+// The body of the whole-solve kernels, on resolved arguments: solve.hip's k_trsm_r calls it with
+// blockIdx.x, batch_apply.hip's k_trsm_r_batch with the base pointers of member blockIdx.y: the same
+// code on the same operands, so the same bits.
+// solve: X <- R^{-T} X (TRANS) or X <- R^{-1} X. The workgroup of `strip` owns columns 64 strip ..
+// + 63, wave w its 16w .. 16w + 15. A wave with no column below nrhs does no arithmetic but takes
+// part in the staging and in every barrier.
+// ---------------------------------------------------------------------------------------
+template <int B, typename S, bool TRANS>
+__device__ __forceinline__ void trsm_r_body(const SolveArgs& a, const int strip, double* lds) {
+  using G = Geo<B>;
+  constexpr int IB = G::IB, NG = G::NG, NRI = G::NRI, NKS = G::NKS;
+  double* Vs = lds;
+
+  const S* A = (const S*)a.A;
+  const size_t lda = a.lda, ldx = a.ldx;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int col0 = strip * 64 + 16 * w, col = col0 + (lane & 15);
+  const bool active = col0 < a.nrhs;  // wave-uniform
+  const bool on = col < a.nrhs;
+  S* Xw = (S*)a.X + (size_t)(active ? col0 : 0) * ldx;
+  const unsigned coff = head_off<B, S>(ldx, 0);
+  double X[NKS];
+
+  // tile (k,k) against X_k: per group (descending for R, ascending for R^T) first the groups
+  // already solved — Z = X_g - (their columns of the group's rows of op(R)) X, the MFMA product over
+  // those k-steps only — then the group's own block by substitution
+  auto diag = [&](int k) {
+    const S* Rt = A + (size_t)k * B * lda + (size_t)k * B;
+    for (int gi = 0; gi < NG; ++gi) {
+      const int g = TRANS ? gi : NG - 1 - gi;
+      __syncthreads();
+      stage_r<B, S, !TRANS, true>(Vs, Rt, lda, g, TRANS ? 0 : g, TRANS ? g + 1 : NG);
+      __syncthreads();
+      if (active) {
+        // (the group's registers by selects on the uniform g: X stays in registers at any NG)
+        double Z[NRI];
+#pragma unroll
+        for (int r = 0; r < NRI; ++r) Z[r] = X[r];
+#pragma unroll
+        for (int gg = 1; gg < NG; ++gg)
+#pragma unroll
+          for (int r = 0; r < NRI; ++r) Z[r] = gg == g ? X[gg * NRI + r] : Z[r];
+        accum_z<B>(Vs, X, Z, TRANS ? 0 : (g + 1) * NRI, TRANS ? g * NRI : NKS);
+        subst<B, TRANS>(Vs + g * IB * G::VP, Z);
+#pragma unroll
+        for (int gg = 0; gg < NG; ++gg)
+#pragma unroll
+          for (int r = 0; r < NRI; ++r) X[gg * NRI + r] = gg == g ? Z[r] : X[gg * NRI + r];
+      }
+    }
+  };
+  // X_i -= (tile Rt of op(R)) X_k: per group the 32 target rows are loaded ahead of the staging,
+  // updated by one pass of accum_z over the whole strip and stored
+  auto update = [&](int i, const S* Rt) {
+    const __amdgpu_buffer_rsrc_t ri = uniform_rsrc(Xw + (size_t)i * B);
+    for (int g = 0; g < NG; ++g) {
+      double H[NRI];
+      const unsigned hoff = coff + (unsigned)(g * IB * (int)sizeof(S));
+      if (active) load_h<B, S>(H, ri, hoff, on);
+      __syncthreads();
+      stage_r<B, S, !TRANS, false>(Vs, Rt, lda, g, 0, NG);
+      __syncthreads();
+      if (active) {
+        accum_z<B>(Vs, X, H, 0, NKS);
+        if (on) store_head_buf<B, S, 0>(H, ri, hoff);
+      }
+    }
+  };
+  auto step = [&](int k) {
+    const __amdgpu_buffer_rsrc_t rk = uniform_rsrc(Xw + (size_t)k * B);
+    if (active) load_x<B, S>(X, rk, coff, on);
+    diag(k);
+    if (active) {
+      // fp32 storage: the updates use X_k as it is stored
+      if constexpr (sizeof(S) == 4) {
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) X[ks] = (double)(float)X[ks];
+      }
+      if (on) store_strip_buf<B, S, 0>(X, rk, coff, 0);
+    }
+  };
+
+  if constexpr (TRANS) {
+    for (int k = 0; k < a.nt; ++k) {
+      step(k);
+      for (int i = k + 1; i < a.nt; ++i) update(i, A + (size_t)i * B * lda + (size_t)k * B);  // R_ki
+    }
+  } else {
+    for (int k = a.nt - 1; k >= 0; --k) {
+      step(k);
+      for (int i = 0; i < k; ++i) update(i, A + (size_t)k * B * lda + (size_t)i * B);  // R_ik
+    }
   }
 }
 

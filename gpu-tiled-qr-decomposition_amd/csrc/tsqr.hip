@@ -9,11 +9,11 @@
 // per-level T workspace, one tqr_apply workspace per domain. C <- Q^T C walks the levels upwards —
 // k_apply_q_batch on the level's domains, k_gather of the domains' top n rows into the next level's
 // C_l — and scatters back down; C <- Q C is the exact reverse.
-// k_apply_t_batch / k_apply_q_batch are apply.hip's kernels (the bodies of apply_dev.hpp) with the
-// domain as a second grid dimension: blockIdx.y's offset is taken in 64 bits on the base pointers, and
-// inside a domain the offsets are the apply's own. A domain therefore has the bytes tqr_apply_q computes
-// on it alone. Every launch here is ordered by its stream only: no flags, counters or waits between
-// workgroups.
+// k_apply_t_batch / k_apply_q_batch (apply_batch_dev.hpp, shared with batch_apply.hip) are apply.hip's
+// kernels (the bodies of apply_dev.hpp) with the domain as a second grid dimension: blockIdx.y's offset
+// is taken in 64 bits on the base pointers, and inside a domain the offsets are the apply's own. A
+// domain therefore has the bytes tqr_apply_q computes on it alone. Every launch here is ordered by its
+// stream only: no flags, counters or waits between workgroups.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "apply.hpp"
+#include "apply_batch_dev.hpp"
 #include "apply_dev.hpp"
 #include "host_common.hpp"
 #include "solve.hpp"
@@ -29,35 +30,7 @@
 
 namespace tqr {
 
-struct ApplyBatchArgs {
-  ApplyArgs a;                       // domain 0 of the launch
-  long long sA, sTau, sC, sTw;       // elements (sTw: doubles) between consecutive domains
-};
-
-template <int B, typename S>
-__device__ __forceinline__ ApplyArgs domain_args(const ApplyBatchArgs& ba) {
-  ApplyArgs a = ba.a;
-  const size_t i = blockIdx.y;
-  a.A = (const S*)a.A + i * (size_t)ba.sA;
-  a.tau = (const S*)a.tau + i * (size_t)ba.sTau;
-  a.C = (S*)a.C + i * (size_t)ba.sC;
-  a.Tw = a.Tw + i * (size_t)ba.sTw;
-  return a;
-}
-
-template <int B, typename S>
-__global__ __launch_bounds__(NT, 1) void k_apply_t_batch(ApplyBatchArgs ba) {
-  extern __shared__ __align__(16) double lds[];
-  const ApplyArgs a = domain_args<B, S>(ba);
-  apply_t_body<B, S>(a, blockIdx.x, lds);
-}
-
-template <int B, typename S, bool TRANS>
-__global__ __launch_bounds__(NT, 2) void k_apply_q_batch(ApplyBatchArgs ba) {
-  extern __shared__ __align__(16) double lds[];
-  const ApplyArgs a = domain_args<B, S>(ba);
-  apply_q_body<B, S, TRANS>(a, blockIdx.x, lds);
-}
+// (ApplyBatchArgs, k_apply_t_batch, k_apply_q_batch: apply_batch_dev.hpp, shared with batch_apply.hip)
 
 // ---------------------------------------------------------------------------------------
 // Gather / scatter: one thread per element, consecutive threads on consecutive rows of a column

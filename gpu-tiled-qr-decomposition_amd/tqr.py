@@ -188,6 +188,24 @@ def lib():
     L.tqr_batch_plan.argtypes = [_I, _I, _I, _I, _I, ctypes.c_size_t, ctypes.POINTER(_I), ctypes.POINTER(_I),
                                  ctypes.POINTER(_I)]
     L.tqr_batch_plan.restype = _I
+    L.tqr_batch_apply_bytes.argtypes = [_I, _I, _I, _I, _I]
+    L.tqr_batch_apply_bytes.restype = ctypes.c_size_t
+    L.tqr_batch_apply_create.argtypes = [ctypes.POINTER(_P), _I, _I, _I, _I, _I]
+    L.tqr_batch_apply_create.restype = _I
+    L.tqr_batch_apply_workspace_bytes.argtypes = [_P]
+    L.tqr_batch_apply_workspace_bytes.restype = ctypes.c_size_t
+    L.tqr_batch_apply_prepare.argtypes = [_P, _P, _I, _LL, _P, _LL, _P]
+    L.tqr_batch_apply_prepare.restype = _I
+    L.tqr_batch_apply_q.argtypes = [_P, _I, _P, _I, _LL, _P, _I, _I, _LL, _P]
+    L.tqr_batch_apply_q.restype = _I
+    L.tqr_batch_form_q.argtypes = [_P, _P, _I, _LL, _P, _I, _I, _LL, _P]
+    L.tqr_batch_form_q.restype = _I
+    L.tqr_batch_trsm_r.argtypes = [_I, _I, _I, _I, _I, _P, _I, _LL, _P, _I, _I, _LL, _P]
+    L.tqr_batch_trsm_r.restype = _I
+    L.tqr_batch_lstsq.argtypes = [_P, _I, _P, _I, _LL, _P, _I, _I, _LL, _P, _LL, _P]
+    L.tqr_batch_lstsq.restype = _I
+    L.tqr_batch_apply_destroy.argtypes = [_P]
+    L.tqr_batch_apply_destroy.restype = None
     _SP = ctypes.POINTER(TsqrSpec)
     L.tqr_tsqr_plan.argtypes = [_SP, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), _I,
                                 ctypes.POINTER(ctypes.c_size_t)]
@@ -941,6 +959,138 @@ def lstsq(F, tau, B, b):
     X = torch.linalg.solve_triangular(Rt, B[:, :n], upper=False, left=False)
     res = torch.linalg.vector_norm(B[:, n:], dim=1)
     return X, res
+
+
+def _batch_layout(who, T, cols, ld, stride):
+    """(cols, ld, stride) of a batch operand: the defaults of a (batch, cols, ld) tensor, or what the
+    caller gives for a flat one (whose length taken for ld would pass the C validation)."""
+    if T.ndim == 3:
+        cols = T.shape[1] if cols is None else cols
+        ld = T.shape[-1] if ld is None else ld
+    elif cols is None or ld is None:
+        raise TQRError(f"{who}: the column count and the leading dimension default to the shape of a "
+                       "(batch, columns, ld) tensor only")
+    return cols, ld, cols * ld if stride is None else stride
+
+
+class BatchedApply:
+    """Apply, form-Q and least squares on every member of a BatchedQR's layout in the launches of one
+    (tqr_batch_apply, include/tqr.h "batched apply and solve"): member i gets the bytes of ApplyQ's
+    calls on it alone. Create once per (m, n, b, dtype, batch) — the handle holds the T images of all
+    members, batch_apply_bytes() of them —, prepare() once per factorisation, then any number of calls.
+    Operands are (batch, columns, ld) tensors with default strides, or flat tensors whose first element
+    is member 0's with ldd*= and stride*= (elements) for any layout of include/tqr.h."""
+
+    def __init__(self, m, n, b, dtype, batch):
+        self.m, self.n, self.b, self.batch = m, n, b, batch
+        self.dtype = dtype if isinstance(dtype, int) else _dtype_code(dtype)
+        self.kmax = min(m, n) // b if b > 0 else 0
+        self.h = None
+        h = _P()
+        check(lib().tqr_batch_apply_create(ctypes.byref(h), m, n, b, self.dtype, batch), "tqr_batch_apply_create")
+        self.h = h
+
+    def workspace_bytes(self):
+        return int(lib().tqr_batch_apply_workspace_bytes(self.h))
+
+    def _same(self, who, *tensors):
+        for t in tensors:
+            if t is not None and _dtype_code(t.dtype) != self.dtype:
+                raise TQRError(f"BatchedApply.{who}: every tensor must be of the handle's dtype")
+
+    def prepare(self, A, tau, ldda=None, strideA=None, strideTau=None, stream=None):
+        """A and tau as BatchedQR.execute left them, with the same ldda / strideA / strideTau. Stream-ordered."""
+        self._same("prepare", A, tau)
+        _, ldda, strideA = _batch_layout("BatchedApply.prepare", A, self.n, ldda, strideA)
+        strideTau = self.kmax * self.m if strideTau is None else strideTau
+        check(lib().tqr_batch_apply_prepare(self.h, _ptr(A), ldda, strideA, _ptr(tau), strideTau, _stream_handle(stream)),
+              "tqr_batch_apply_prepare")
+
+    def apply(self, A, C, trans=True, nrhs=None, ldda=None, lddc=None, strideA=None, strideC=None, stream=None):
+        """C_i (nrhs, lddc) <- Q_i^T C_i (trans) or Q_i C_i in place, for every member. Stream-ordered."""
+        self._same("apply", A, C)
+        _, ldda, strideA = _batch_layout("BatchedApply.apply", A, self.n, ldda, strideA)
+        nrhs, lddc, strideC = _batch_layout("BatchedApply.apply", C, nrhs, lddc, strideC)
+        check(lib().tqr_batch_apply_q(self.h, 1 if trans else 0, _ptr(A), ldda, strideA, _ptr(C), nrhs, lddc, strideC,
+                                      _stream_handle(stream)), "tqr_batch_apply_q")
+
+    def form_q(self, A, Q, ncols=None, ldda=None, lddq=None, strideA=None, strideQ=None, stream=None):
+        """Q_i (ncols, lddq) <- the first ncols columns of member i's Q, 1 <= ncols <= m; Q is output-only."""
+        self._same("form_q", A, Q)
+        _, ldda, strideA = _batch_layout("BatchedApply.form_q", A, self.n, ldda, strideA)
+        ncols, lddq, strideQ = _batch_layout("BatchedApply.form_q", Q, ncols, lddq, strideQ)
+        check(lib().tqr_batch_form_q(self.h, _ptr(A), ldda, strideA, _ptr(Q), ncols, lddq, strideQ, _stream_handle(stream)),
+              "tqr_batch_form_q")
+
+    def lstsq(self, A, B, trans=False, nrhs=None, ldda=None, lddb=None, strideA=None, strideB=None, res=None,
+              strideRes=None, stream=None):
+        """ApplyQ.lstsq on every member (m >= n): B_i in place; res (optional): member i's nrhs residual
+        norms at element i * strideRes (default nrhs). Stream-ordered."""
+        self._same("lstsq", A, B, res)
+        _, ldda, strideA = _batch_layout("BatchedApply.lstsq", A, self.n, ldda, strideA)
+        nrhs, lddb, strideB = _batch_layout("BatchedApply.lstsq", B, nrhs, lddb, strideB)
+        strideRes = nrhs if strideRes is None else strideRes
+        pres = None if res is None else _ptr(res)
+        check(lib().tqr_batch_lstsq(self.h, 1 if trans else 0, _ptr(A), ldda, strideA, _ptr(B), nrhs, lddb, strideB, pres,
+                                    strideRes, _stream_handle(stream)), "tqr_batch_lstsq")
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().tqr_batch_apply_destroy(self.h)
+        except Exception:
+            pass
+
+
+def batch_apply_bytes(m, n, b, dtype, batch):
+    """Host-only: the workspace a BatchedApply of these arguments allocates (tqr_batch_apply_bytes);
+    bad arguments raise."""
+    dtype = dtype if isinstance(dtype, int) else _dtype_code(dtype)
+    nb = int(lib().tqr_batch_apply_bytes(m, n, b, dtype, batch))
+    if nb == 0:
+        raise TQRError(f"tqr_batch_apply_bytes: invalid arguments {(m, n, b, dtype, batch)}")
+    return nb
+
+
+def trsm_r_batched(F, X, b, trans=False, n=None, nrhs=None, batch=None, ldda=None, lddx=None, strideA=None, strideX=None,
+                   stream=None):
+    """X_i <- R_i^{-1} X_i (or R_i^{-T} X_i with trans) in place for every member of a batch
+    (tqr_batch_trsm_r): trsm_r's bytes per member, no handle, no workspace. F (batch, >= n, ldda) and X
+    (batch, nrhs, lddx) with default strides, or flat tensors with n, nrhs, batch, ldd* and stride*."""
+    if X.dtype != F.dtype:
+        raise TQRError("trsm_r_batched: F and X must be of one dtype")
+    if batch is None:
+        if F.ndim != 3:
+            raise TQRError("trsm_r_batched: batch defaults to the first dimension of a (batch, columns, ld) tensor only")
+        batch = F.shape[0]
+    fcols, ldda, strideA = _batch_layout("trsm_r_batched", F, None if F.ndim == 3 else n, ldda, strideA)
+    n = fcols if n is None else n
+    nrhs, lddx, strideX = _batch_layout("trsm_r_batched", X, nrhs, lddx, strideX)
+    check(lib().tqr_batch_trsm_r(_dtype_code(F.dtype), 1 if trans else 0, n, b, batch, _ptr(F), ldda, strideA, _ptr(X), nrhs,
+                                 lddx, strideX, _stream_handle(stream)), "tqr_batch_trsm_r")
+
+
+def lstsq_batched(A, B, b):
+    """One-shot batched least squares min |A_i x - b| for every column of every B_i: A (batch, n, m)
+    and B (batch, nrhs, m) contiguous device tensors of one dtype, m >= n. Factorises a copy of A with
+    a BatchedQR and solves with a BatchedApply; A and B are not modified. Returns (X (batch, nrhs, n),
+    res (batch, nrhs), F, tau): F and tau as BatchedQR.execute leaves them."""
+    import torch
+    if A.ndim != 3 or B.ndim != 3 or B.shape[0] != A.shape[0] or B.shape[-1] != A.shape[-1] or B.dtype != A.dtype:
+        raise TQRError("lstsq_batched: A must be (batch, n, m) and B (batch, nrhs, m), of one dtype")
+    batch, n, m = A.shape
+    if m < n:
+        raise TQRError(f"lstsq_batched needs m >= n, got {m} x {n}")
+    bq = BatchedQR(m, n, b, A.dtype, batch)
+    ba = BatchedApply(m, n, b, A.dtype, batch)
+    F, Y = A.clone().contiguous(), B.clone().contiguous()
+    tau = torch.zeros((batch, bq.kmax, m), dtype=A.dtype, device=A.device)
+    res = torch.empty((batch, B.shape[1]), dtype=A.dtype, device=A.device)
+    cs = torch.cuda.current_stream()
+    bq.execute(F, tau, stream=cs)
+    ba.prepare(F, tau, stream=cs)
+    ba.lstsq(F, Y, res=res, stream=cs)
+    return Y[:, :, :n], res, F, tau
 
 
 def lstsq_fused(A, B, b, solve=None):

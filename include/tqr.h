@@ -449,7 +449,8 @@ int tqr_lstsq_pipe(tqr_apply_pipe* pp, tqr_solve* sv, tqr_apply* ap, int trans, 
  * Use of the other handles: because of the bit contract every handle of this library works on a
  * batch member unchanged, through an offset base pointer — tqr_apply_* (prepare on dA + i * strideA,
  * ldda, dtau_compact + i * strideTau), tqr_trsm_r, tqr_lstsq*, the pipelined solve and apply, and
- * tqr_apply_pipe_form_q. There is no batched apply or solve.
+ * tqr_apply_pipe_form_q. For all members in one call: tqr_batch_apply_* and tqr_batch_trsm_r below
+ * ("batched apply and solve"), with the per-member calls' bytes.
  * Method: the wave engine runs every BFS wave of the reference DAG as two launches (panel tasks,
  * update strips; tqr_engine above) whose workgroups are independent of each other. The batched call
  * issues the same launches with the matrix as a second grid dimension, so the launch count is that
@@ -498,6 +499,82 @@ int tqr_batch_execute(tqr_batch* bt, void* dA, int ldda, long long strideA, void
 void tqr_batch_destroy(tqr_batch* bt);
 int tqr_batch_plan(int m, int n, int b, int dtype, int batch, size_t ws_limit, int* group, int* ngroups, int* nlaunch);
 
+/* ---- batched apply and solve: Q, Q^T, form-Q, the solve with R and least squares on a whole batch ---
+ * What tqr_apply_* / tqr_trsm_r / tqr_lstsq do on one factorisation, on every member of a batch that
+ * tqr_batch_execute factorised, in the launches of one member: a loop over the members issues 3 * batch
+ * launches of one or two workgroups each (per 64 right-hand sides), the batched call issues 3 launches
+ * with the member as a second grid dimension.
+ * Layouts: member i of A and of the compact taus sits where tqr_batch_execute put it — dA + i * strideA
+ * under ldda, dtau_compact + i * strideTau, the same two stride forms for strideA, strideTau >= m * kmax
+ * always. C (m x nrhs), Q (m x ncols), B (m x nrhs) and X (n x nrhs) take the same two forms with their
+ * own row and column counts, under their own leading dimension ld >= rows:
+ *   stacked          stride >= (cols-1) * ld + rows;
+ *   row-interleaved  stride >= rows and (batch-1) * stride + rows <= ld.
+ * With batch == 1 the strides are ignored. tqr_batch_trsm_r's A is the leading n x n of a member: ldda
+ * >= n and the forms with rows = cols = n (every layout tqr_batch_execute accepts for m >= n is one).
+ * dres member i is nrhs elements at dres + i * strideRes; strideRes >= nrhs when batch > 1; dres may be
+ * NULL (strideRes is then not looked at). Stride arithmetic is in 64 bits on the base pointers; inside a
+ * member the 32-bit offset rules and the leading-dimension bound of the per-member calls hold.
+ * Bit contract: member i has the bytes of the per-member call on it alone, because the same kernel
+ * body runs on the same operands behind a per-member pointer offset:
+ *   tqr_batch_apply_q   tqr_apply_q on a handle prepared on member i;
+ *   tqr_batch_trsm_r    tqr_trsm_r;
+ *   tqr_batch_lstsq     tqr_lstsq: X, the rest of Q^T B, the zeroed rows of TQR_TRANS, dres (TQR_NOTRANS
+ *                       only, as there);
+ *   tqr_batch_form_q    tqr_apply_q(TQR_NOTRANS) on a buffer holding the first ncols columns of I_m,
+ *                       1 <= ncols <= m (ncols = min(m, n): the thin Q; ncols = m: the full one).
+ * tqr_batch_form_q is output-only: dQ need not be initialised — the call fills the identity's columns
+ * itself and then applies Q; the work on the identity's zero blocks is done, as in tqr_tsqr_form_q (not
+ * skipped as in tqr_apply_pipe_form_q). The bytes do not depend on batch, the strides, the base address
+ * or the stream. Nothing outside the members is written: rows beyond a member, the gaps between
+ * members, columns >= nrhs or ncols. What is read as a value is the per-member calls' rule, word for
+ * word: R on and above the diagonal of a diagonal tile is never read by the apply, and V (everything
+ * below the diagonal) is never read by the solve — either may hold anything, inf and NaN included.
+ * Workspace: the handle holds the T images of all members, batch * tqr_apply_workspace_bytes of the
+ * shape, so one prepare serves any number of applies. There are no groups: tqr_batch_apply_bytes (host
+ * only, no GPU; 0 on bad arguments) tells a caller beforehand when to split a batch through offset
+ * pointers. create allocates it (TQR_ENOMEM if that fails); no other call allocates. tqr_batch_trsm_r
+ * needs no handle and no workspace.
+ * Ordering: a plan's, as tqr_tsqr_*. Concurrent host threads are mutually excluded while they
+ * enqueue, and every call's stream first waits for the handle's previous call, whatever its stream (a
+ * prepare rewrites the T images the applies read). Calls return once all is enqueued.
+ * tqr_batch_trsm_r is ordered by its stream alone. Every kernel of these calls is ordered by its launch
+ * alone — no flags, counters or waits between workgroups. More members than a grid's y dimension
+ * (65535) run as consecutive launches with advanced base pointers.
+ * Errors: TQR_EINVAL before any device call for tqr_apply_create's own argument errors, batch < 1, a
+ * shape whose prepare grid (one workgroup per T image of a member) would pass 2^31 or whose workspace a
+ * size_t, a NULL handle or pointer, a bad trans, nrhs < 1, ncols outside 1 .. m, a leading dimension
+ * below the member's rows or beyond the library's bound, a stride of neither form, strideTau < m * kmax,
+ * strideRes < nrhs, tqr_batch_lstsq with m < n. Without a gfx950, create still returns a handle with
+ * no device memory, workspace_bytes answers, and every enqueueing call returns TQR_ENODEV after that
+ * validation (tqr_batch_trsm_r too). With a device, any call on a handle other than prepare before its
+ * first successful prepare returns TQR_EINVAL, before any device call.
+ * Measured on an MI355X (tools/batch_apply_bench.py), TQR_NOTRANS least squares with
+ * dres, against a loop of tqr_lstsq over per-member prepared tqr_apply handles in the same run, equal
+ * bytes: 64 factorisations of 512 x 512, b = 64, fp64, 64 right-hand sides each: 0.81 against 47.3 ms;
+ * 1024 of them: 2.75 against 851.7 ms; 1024 of 1024 x 1024, b = 128: 7.50 against 2138 ms; 256 of 4096 x
+ * 256, b = 128, one right-hand side: 2.05 against 499.5 ms. tqr_batch_apply_prepare against the loop of
+ * tqr_apply_prepare: 0.14 against 0.81, 1.48 against 14.4, 5.80 against 19.2 and 2.22 against 4.68 ms.
+ * From 16 members on the batched calls were faster at all 40 points measured (lstsq 13.5 to 745 x,
+ * prepare 1.24 to 19.4 x). For ONE factorisation tqr_lstsq on a tqr_apply handle is the faster call
+ * (0.164 against 0.195 ms at 256 x 256, 1.64 against 1.65 ms at 4096 x 256): the batched handle adds an
+ * event wait and record per call. TQR_TRANS, the apply and form-Q alone were not measured. */
+typedef struct tqr_batch_apply tqr_batch_apply;
+size_t tqr_batch_apply_bytes(int m, int n, int b, int dtype, int batch);
+int tqr_batch_apply_create(tqr_batch_apply** ba, int m, int n, int b, int dtype, int batch);
+size_t tqr_batch_apply_workspace_bytes(const tqr_batch_apply* ba);
+int tqr_batch_apply_prepare(tqr_batch_apply* ba, const void* dA, int ldda, long long strideA, const void* dtau_compact,
+                            long long strideTau, void* stream);
+int tqr_batch_apply_q(tqr_batch_apply* ba, int trans, const void* dA, int ldda, long long strideA, void* dC, int nrhs,
+                      int lddc, long long strideC, void* stream);
+int tqr_batch_form_q(tqr_batch_apply* ba, const void* dA, int ldda, long long strideA, void* dQ, int ncols, int lddq,
+                     long long strideQ, void* stream);
+int tqr_batch_trsm_r(int dtype, int trans, int n, int b, int batch, const void* dA, int ldda, long long strideA, void* dX,
+                     int nrhs, int lddx, long long strideX, void* stream);
+int tqr_batch_lstsq(tqr_batch_apply* ba, int trans, const void* dA, int ldda, long long strideA, void* dB, int nrhs,
+                    int lddb, long long strideB, void* dres, long long strideRes, void* stream);
+void tqr_batch_apply_destroy(tqr_batch_apply* ba);
+
 /* ---- tall-skinny: QR of an m x n matrix, m >> n, as a tree of batched factorisations (TSQR) -------
  * The flat tile tree of tqr_plan_execute is one GEQRT and m/b - 1 TSQRTs in series per panel: on a
  * tall-skinny matrix the device idles behind one CU. tqr_tsqr_factor cuts A into D_0 = m / m_dom row
@@ -537,7 +614,8 @@ int tqr_batch_plan(int m, int n, int b, int dtype, int batch, size_t ws_limit, i
  * Bit contract: after tqr_tsqr_factor every domain of every level has the bytes of tqr_batch_execute on
  * that layout, i.e. of a TQR_ENGINE_WAVES plan on the member alone — except the upper triangle of
  * dA[0:n, 0:n], which holds the final R. tqr_tsqr_apply_q on a domain computes the bytes of tqr_apply_q
- * on that member (the same kernel bodies behind a per-domain pointer offset). Nothing outside the
+ * on that member (the same kernel bodies behind a per-domain pointer offset: the kernels are the ones
+ * tqr_batch_apply_prepare / tqr_batch_apply_q launch, shared between the two). Nothing outside the
  * matrices is written: rows >= m, columns >= n or nrhs, the padding of ldda / lddc.
  * Zero padding is harmless by the tile kernels' conventions: a TSQRT on [R_kk; 0] gives V_B = 0 and
  * tau = 2 (no scaling when |x| == 0), and zero rows of a right-hand side stay zero.
