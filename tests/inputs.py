@@ -13,8 +13,10 @@ import numpy as np
 
 P = ctypes.c_void_p
 # (m, n, b): the smallest shapes at which each mechanism exists — one reflector group per tile; two;
-# four; the production tile (8 groups); wide (kmax = p); a TS chain of 9 under one panel (more than
-# one default chain segment of 8)
+# four; the production tile (8 groups); wide (kmax = p); a TS chain of 9 under one panel. Under the
+# default knobs fp64 storage runs that chain one TSMQR per task (flowplan.cpp default_tail: every step
+# of a plan of at most 32 tile rows is a tail step), not as the segments of 8 and 1 it was chosen for:
+# those run under TQR_TAIL=0 as case T0-128 of tests/segments.py (test_gpu_segments.py)
 SHAPES = [(96, 64, 32), (192, 128, 64), (384, 256, 128), (768, 512, 256), (256, 384, 128), (1280, 256, 128)]
 SHAPES32 = [(192, 128, 64), (768, 512, 256)]
 ACC_SHAPES = [(192, 128, 64), (768, 512, 256)]

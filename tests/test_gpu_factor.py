@@ -50,7 +50,8 @@ def test_factor_vs_reference(tqr, oracle, name):
     (1024, 768, 128, np.float64),
     (768, 1024, 128, np.float64),
     (1024, 1024, 256, np.float64),
-    (2048, 512, 256, np.float64),    # tall-skinny, flat TS chain of 8
+    (2048, 512, 256, np.float64),    # tall-skinny: 7 TS rows under the panel, one TSMQR per chain task under the
+                                     # default knobs (default_tail); chain tasks of several: test_gpu_segments.py
     (512, 512, 64, np.float32),
     (1024, 1024, 256, np.float32),
     (1024, 768, 128, np.float32),    # fp32 asm chain, 128-tiles
