@@ -227,6 +227,24 @@ def lib():
     L.tqr_tsqr_level.restype = _I
     L.tqr_tsqr_destroy.argtypes = [_P]
     L.tqr_tsqr_destroy.restype = None
+    L.tqr_update_create.argtypes = [ctypes.POINTER(_P), _I, _I, _I, _I]
+    L.tqr_update_create.restype = _I
+    L.tqr_update_workspace_bytes.argtypes = [_P]
+    L.tqr_update_workspace_bytes.restype = ctypes.c_size_t
+    L.tqr_update_rows.argtypes = [_P, _P, _I, _P, _I, _P, _P]
+    L.tqr_update_rows.restype = _I
+    L.tqr_update_prepare.argtypes = [_P, _P, _I, _P, _P]
+    L.tqr_update_prepare.restype = _I
+    L.tqr_update_apply_q.argtypes = [_P, _I, _P, _I, _P, _I, _P, _I, _I, _P]
+    L.tqr_update_apply_q.restype = _I
+    L.tqr_update_lstsq.argtypes = [_P, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _P, _I, _P, _P]
+    L.tqr_update_lstsq.restype = _I
+    L.tqr_update_destroy.argtypes = [_P]
+    L.tqr_update_destroy.restype = None
+    L.tqr_update_plan.argtypes = [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I)]
+    L.tqr_update_plan.restype = _I
+    L.tqr_update_level_items.argtypes = [_I, _I, _I, _I, _P, _I]
+    L.tqr_update_level_items.restype = _I
     _lib = L
     return L
 
@@ -1271,6 +1289,102 @@ def tsqr_plan(m, n, b, dtype, m_dom=0, fan=0, nrhs_max=0, ws_limit=0):
     check(lib().tqr_tsqr_plan(ctypes.byref(spec), ctypes.byref(md), ctypes.byref(f), ctypes.byref(nl), dom, 32,
                               ctypes.byref(ws)), "tqr_tsqr_plan")
     return md.value, f.value, nl.value, list(dom[:nl.value]), int(ws.value)
+
+
+# ---- row update: append rows to a finished QR ---------------------------------------------------
+class RowUpdate:
+    """Append mw rows to the R of a finished n-column factorisation (tqr_update, include/tqr.h "row
+    update"): R'^T R' = R^T R + W^T W by the flat-tree TSQRT / TSMQR on the tiles that exist. Create once
+    per (n, mw, b, dtype); update() any number of times. Tensors follow the module convention: R
+    (n, lddr) with the triangle in R[j, i], i <= j; W (n, lddw) the new rows, column-major; tau (q, mw).
+    After an update the Q of the whole is diag(Q_old, I) Q_u: apply() is Q_u alone, on a pair of blocks."""
+
+    def __init__(self, n, mw, b, dtype):
+        self.n, self.mw, self.b = n, mw, b
+        self.dtype = dtype if isinstance(dtype, int) else _dtype_code(dtype)
+        self.q = n // b if b > 0 else 0
+        self.h = None
+        h = _P()
+        check(lib().tqr_update_create(ctypes.byref(h), n, mw, b, self.dtype), "tqr_update_create")
+        self.h = h
+
+    def workspace_bytes(self):
+        return int(lib().tqr_update_workspace_bytes(self.h))
+
+    def _same(self, who, *tensors):
+        for t in tensors:
+            if t is not None and _dtype_code(t.dtype) != self.dtype:
+                raise TQRError(f"{who}: every tensor must be of the handle's dtype")
+
+    def update(self, R, W, tau, lddr=None, lddw=None, stream=None):
+        """R <- R' in place (only its upper triangle is read or written), W <- the TSQRT V tiles, tau
+        (q, mw) <- their taus; then the T pass of prepare(). Stream-ordered."""
+        self._same("RowUpdate.update", R, W, tau)
+        lddr = lddr or R.shape[-1]
+        lddw = lddw or W.shape[-1]
+        check(lib().tqr_update_rows(self.h, _ptr(R), lddr, _ptr(W), lddw, _ptr(tau), _stream_handle(stream)),
+              "tqr_update_rows")
+
+    def prepare(self, W, tau, lddw=None, stream=None):
+        """Rebuild the apply's T images from a stored update (W, tau). Stream-ordered."""
+        self._same("RowUpdate.prepare", W, tau)
+        lddw = lddw or W.shape[-1]
+        check(lib().tqr_update_prepare(self.h, _ptr(W), lddw, _ptr(tau), _stream_handle(stream)), "tqr_update_prepare")
+
+    def apply(self, W, Ctop, Cnew, trans=True, nrhs=None, lddw=None, lddct=None, lddcn=None, stream=None):
+        """[Ctop (nrhs, lddct); Cnew (nrhs, lddcn)] <- Q_u^T (trans) or Q_u of the pair, in place."""
+        self._same("RowUpdate.apply", W, Ctop, Cnew)
+        lddw = lddw or W.shape[-1]
+        lddct = lddct or Ctop.shape[-1]
+        lddcn = lddcn or Cnew.shape[-1]
+        nrhs = Ctop.shape[0] if nrhs is None else nrhs
+        check(lib().tqr_update_apply_q(self.h, 1 if trans else 0, _ptr(W), lddw, _ptr(Ctop), lddct, _ptr(Cnew), lddcn, nrhs,
+                                       _stream_handle(stream)), "tqr_update_apply_q")
+
+    def lstsq(self, R, W, tau, D, Bnew, X, res=None, nrhs=None, lddr=None, lddw=None, lddd=None, lddb=None, lddx=None,
+              stream=None):
+        """One step of recursive least squares (tqr_update_lstsq): update(R, W, tau); (D, Bnew) <- Q_u^T
+        of them; X <- R'^{-1} D; res (optional, nrhs running residual norms) <- sqrt(res^2 + |Bnew'|^2).
+        D (nrhs, lddd) holds the top n rows of Q^T b so far, Bnew (nrhs, lddb) the new rows' right-hand
+        sides, X (nrhs, lddx) receives the solution over all rows so far. Stream-ordered."""
+        self._same("RowUpdate.lstsq", R, W, tau, D, Bnew, X, res)
+        lddr = lddr or R.shape[-1]
+        lddw = lddw or W.shape[-1]
+        lddd = lddd or D.shape[-1]
+        lddb = lddb or Bnew.shape[-1]
+        lddx = lddx or X.shape[-1]
+        nrhs = D.shape[0] if nrhs is None else nrhs
+        pres = None if res is None else _ptr(res)
+        check(lib().tqr_update_lstsq(self.h, _ptr(R), lddr, _ptr(W), lddw, _ptr(tau), _ptr(D), lddd, _ptr(Bnew), lddb, nrhs,
+                                     _ptr(X), lddx, pres, _stream_handle(stream)), "tqr_update_lstsq")
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().tqr_update_destroy(self.h)
+        except Exception:
+            pass
+
+
+def update_plan(n, mw, b):
+    """Host-only: (nlevels, npanel, nupdate, nlaunch) of a RowUpdate of these arguments (tqr_update_plan)."""
+    nl, np_, nu, nla = _I(), _I(), _I(), _I()
+    check(lib().tqr_update_plan(n, mw, b, ctypes.byref(nl), ctypes.byref(np_), ctypes.byref(nu), ctypes.byref(nla)),
+          "tqr_update_plan")
+    return nl.value, np_.value, nu.value, nla.value
+
+
+def update_level_items(n, mw, b, level):
+    """Host-only: the items of one level of the update's schedule as (type, strip, l, j, k) tuples, the
+    TSQRT items (type 2, j = k) first, then the TSMQR strip items (type 3) (tqr_update_level_items)."""
+    cnt = lib().tqr_update_level_items(n, mw, b, level, None, 0)
+    if cnt < 0:
+        check(cnt, "tqr_update_level_items")
+    buf = (_I * (4 * max(cnt, 1)))()
+    got = lib().tqr_update_level_items(n, mw, b, level, buf, cnt)
+    if got < 0:
+        check(got, "tqr_update_level_items")
+    return [(buf[4 * i] & 0xff, buf[4 * i] >> 8, buf[4 * i + 1], buf[4 * i + 2], buf[4 * i + 3]) for i in range(cnt)]
 
 
 # ---- single tile ops (host pointers; the reference's SGEQRF/SLARFT/STSQRF/SSSRFT) --------

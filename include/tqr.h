@@ -662,6 +662,97 @@ int tqr_tsqr_lstsq(tqr_tsqr* ts, int trans, const void* dA, int ldda, void* dB, 
 int tqr_tsqr_level(const tqr_tsqr* ts, int level, void** dW, int* ldw, void** dtau, int* dom_rows, int* ndom);
 void tqr_tsqr_destroy(tqr_tsqr* ts);
 
+/* ---- row update: append rows to a finished QR (qrinsert for rows, recursive least squares) ------
+ * R is the upper triangle of the leading n x n block of a device matrix dR (lddr >= n), as any engine
+ * of this library left it; W (dW, mw x n, lddw >= mw) holds mw new rows. b in {16, 32, 64, 128, 256}
+ * divides n and mw (a caller with fewer rows pads W with zero rows); q = n/b, wt = mw/b.
+ * tqr_update_rows replaces R by the R' of the stacked [R; W]:
+ *   for k in 0..q-1: for l in 0..wt-1:
+ *     TSQRT(R_kk, W_lk) -> R_kk's triangle, V in W_lk, b taus
+ *     for j in k+1..q-1: TSMQR(V = W_lk; R_kj, W_lj)
+ * the flat-tree update restricted to the tiles that exist. On exit R'^T R' = R^T R + W^T W, W holds the
+ * dense TSQRT V tiles, and dtau_u (mw x q column-major, leading dimension mw, of the handle's dtype)
+ * holds at (l*b + c, k) the tau of column c of TSQRT(., W_lk). With the Householder convention above
+ * diag(R') has the sign of diag(R) times (-1)^wt.
+ * Of dR only elements (i, j), i <= j < n, are read or written: the strictly lower part of every
+ * diagonal tile keeps its bytes (the old GEQRT V, NaN and inf included, never enters a product), and
+ * the tiles below the block diagonal are never touched — the rule of tqr_trsm_r. Rows >= mw of dW's
+ * allocation and columns >= n are not touched.
+ * After an update the old V of dR no longer belongs to R': the Q of the updated factorisation of
+ * [A; W] is diag(Q_old, I) * Q_u, where Q_old is the Q of the factorisation that left R (its V and
+ * taus are unchanged and its tqr_apply_* reads nothing else of dR, so that handle still applies
+ * Q_old from dR, prepared before or after the update) and Q_u, (n+mw) x (n+mw), is this
+ * update's, applied by tqr_update_apply_q to a pair (Ctop: n x nrhs, Cnew: mw x nrhs):
+ *   TQR_TRANS:   for k ascending, l ascending: [Ctop_k; Cnew_l] <- TSMQR(V = W_lk) [Ctop_k; Cnew_l];
+ *   TQR_NOTRANS: the exact reverse, each block reflector untransposed, so Q_u (Q_u^T C) = C.
+ * Q^T [c; c_new] of the whole is Q_old^T on c, then Q_u^T on the pair; Q is the reverse order.
+ * Bit contract (the separation identity): in the flat-tree factorisation of the stacked S = [G; W], G
+ * n x n, the tile operations on the W rows never feed those on the G rows, and at step k they see G's
+ * own final R_kk and R_kj. So a TQR_ENGINE_WAVES plan on S equals a wave plan on G followed by
+ * tqr_update_rows with W, bit for bit: the upper triangle, rows >= n (W's V) and rows >= n of the
+ * compact tau (= dtau_u). Likewise tqr_apply_q of the stacked factorisation equals G's tqr_apply_q
+ * then tqr_update_apply_q (TQR_TRANS; reversed for TQR_NOTRANS), both with T from prepare passes.
+ * fp32 handles load and store float and compute in fp64, as the wave engine.
+ * Method: level-synchronous, as the wave engine. TSQRT(l,k) sits on level 2k + l, TSMQR(l,j,k) on
+ * level 2k + l + 1; every dependency lies on an earlier level and the items of one level touch
+ * disjoint data. Each level is at most two launches (the TSQRTs, one workgroup each; the 64-column
+ * strips of the TSMQRs) on two side streams of the handle joined by events to the caller's stream.
+ * No kernel waits for another workgroup: no flags, no counters, nothing that can hang. The critical
+ * path is 2q + wt - 2 levels, each at least one TSQRT long: the update pays when wt is small against
+ * q. For mw >> n it is a serial chain of wt TSQRTs per step — factorise such a block first
+ * (tqr_tsqr_* or a plan) and append its R.
+ * Measured on an MI355X (tools/update_bench.py), n = 16384, b = 256, against a flow plan
+ * on the stacked (n + mw) x n matrix from scratch and a wave plan on the dense [R; W], in the same run:
+ * fp64, mw = 256: 48.2 ms against 118.6 and 226.2 ms; mw = 1024: 83.6 against 125.6 and 235.1 ms; mw =
+ * 4096: 115.5 against 153.9 and 291.5 ms. The update LOSES in fp32 (mw = 1024: 91.1 ms against the flow
+ * plan's 70.5 ms, whose fp32 chains run on the fp32 MFMA; 249.1 ms for the dense wave plan).
+ * tqr_update_apply_q on 64 columns: 9.7 / 41.7 / 201.5 ms (one workgroup walks q * wt TSMQRs);
+ * tqr_update_lstsq with 64 right-hand sides: 182.4 / 250.1 / 441.7 ms, of which tqr_trsm_r on one
+ * workgroup is 124 ms. mw > n/4, other n and b were not measured.
+ * tqr_update_rows ends with the T pass of tqr_update_prepare, so the handle is ready for applies.
+ * tqr_update_prepare rebuilds the apply's T images from stored W and dtau_u alone (how one
+ * re-attaches a handle to an update kept from earlier); tqr_update_apply_q before any prepare or rows
+ * returns TQR_EINVAL. nrhs >= 1 need not be a multiple of anything; rows and columns outside the two
+ * blocks are untouched. One workgroup per 64 columns walks the q * wt TSMQRs serially.
+ * tqr_update_lstsq: one step of recursive least squares. dD (n x nrhs, lddd >= n, in/out) holds the
+ * top n rows of Q^T b so far; dBnew (mw x nrhs, lddb >= mw) the new right-hand-side rows on entry,
+ * their transformed rows on exit. In order: tqr_update_rows; tqr_update_apply_q(TQR_TRANS) on (dD,
+ * dBnew); a copy of dD to dX (n x nrhs, lddx >= n; dX must not overlap dD); tqr_trsm_r(TQR_NOTRANS)
+ * on dX with R' — dX is the solution over all rows so far. dres: NULL, or nrhs running residual norms
+ * of the handle's dtype, dres[j] <- sqrt(dres[j]^2 + |Bnew'[:, j]|^2), the sum accumulated in fp64 in
+ * a fixed order and unscaled, as tqr_lstsq's norm (start it from tqr_lstsq's dres, or zeros).
+ * Workspace: two sets of T images (the factorisation's and the apply's), one 32 x 33 fp64 image (b <
+ * 32: b x (b+1)) padded to whole KiB per 32-reflector group of each of the q * wt W tiles —
+ * tqr_update_workspace_bytes, allocated by create; nothing is allocated afterwards.
+ * Ordering: as a plan's. Calls of one handle are mutually excluded while they enqueue; each call's
+ * stream first waits for the handle's previous rows / prepare, and a rows / prepare for every apply
+ * enqueued since; applies may overlap each other. Everything is stream-ordered.
+ * Errors: TQR_EINVAL before any device call for a bad dtype, a bad b or one that does not divide n
+ * and mw, n <= 0 or mw <= 0, a NULL handle or pointer, a bad trans, nrhs < 1, lddr < n, lddw, lddcn or
+ * lddb below mw, lddct, lddd or lddx below n, and any leading dimension (n and mw included) beyond
+ * the library's bound. A missing or non-gfx950 device is reported after that validation:
+ * tqr_update_create then still returns a handle (without device memory; workspace_bytes answers), and
+ * rows, prepare and lstsq on it return TQR_ENODEV.
+ * tqr_update_plan, tqr_update_level_items (host only, no GPU): the schedule the host side issues.
+ * *nlevels = 2q + wt - 2, *npanel = q * wt TSQRT items, *nupdate = ceil(b/64) * wt * q(q-1)/2 TSMQR
+ * strip items, *nlaunch = the non-empty TSQRT launches plus the non-empty TSMQR launches of all levels
+ * plus 1 (the closing T pass). Outputs may be NULL. tqr_update_level_items writes the items of one
+ * level, 4 ints each {type | strip << 8, l, j, k} (type 2 = TSQRT with j = k, type 3 = TSMQR; the
+ * TSQRT items first), at most `cap` of them, and returns the level's item count. Arguments out of
+ * range return TQR_EINVAL and write nothing. */
+typedef struct tqr_update tqr_update;
+int tqr_update_create(tqr_update** up, int n, int mw, int b, int dtype);
+size_t tqr_update_workspace_bytes(const tqr_update* up);
+int tqr_update_rows(tqr_update* up, void* dR, int lddr, void* dW, int lddw, void* dtau_u, void* stream);
+int tqr_update_prepare(tqr_update* up, const void* dW, int lddw, const void* dtau_u, void* stream);
+int tqr_update_apply_q(tqr_update* up, int trans, const void* dW, int lddw, void* dCtop, int lddct, void* dCnew,
+                       int lddcn, int nrhs, void* stream);
+int tqr_update_lstsq(tqr_update* up, void* dR, int lddr, void* dW, int lddw, void* dtau_u, void* dD, int lddd,
+                     void* dBnew, int lddb, int nrhs, void* dX, int lddx, void* dres, void* stream);
+void tqr_update_destroy(tqr_update* up);
+int tqr_update_plan(int n, int mw, int b, int* nlevels, int* npanel, int* nupdate, int* nlaunch);
+int tqr_update_level_items(int n, int mw, int b, int level, int* items, int cap);
+
 /* ---- multi-GPU: tile-column partition, one process per GPU ---------------------------------
  * Rank r owns the tile columns j with tqr_dist_owner(j) == r — snake order over the ranks
  * (0..W-1, W-1..0, 0..W-1, ...: every rank's columns sum to the same index total, balancing the
